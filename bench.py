@@ -25,6 +25,14 @@ tokens of work per GPU per step.  On one GPU the step is captured as one HIP
 graph during the warmup (``--hip-graph``; needs ``--warmup >= 3``) and
 replayed for the K timed steps, each replay a full step with fresh dropout
 masks and the scheduler's learning rate.
+
+A plain run does only what the headline figure needs: setup, warmup, the K
+timed steps, the result line.  ``--dump-outputs DIR`` adds, after the timed
+steps, ``DIR/loss.npy`` and ``DIR/params_sample.npy`` (the last step's loss and
+a seeded sample of the parameters it updated; tokens, initial weights and
+dropout salts are seeded, so two builds can be compared output for output).
+``--full`` is where measurements beyond the headline figure belong; there are
+none today, so it changes nothing yet.
 """
 import argparse
 import json
@@ -84,7 +92,48 @@ def parse():
                     help="capture the whole step in one HIP graph (1/0; default: on for one "
                          "GPU when --warmup >= 3 covers the capture; the forward-overlapped "
                          "AdamW then runs deferred inside the captured step)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed as "
+                         "DIR/<name>.npy: loss.npy (the loss the step returned) and "
+                         "params_sample.npy (a fixed seeded sample of every parameter it "
+                         "updated); with the same arguments the inputs repeat run to run")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline figure (none today: "
+                         "a plain run already does only setup, warmup, the timed steps and "
+                         "the result line; new side measurements go behind this flag)")
     return ap.parse_args()
+
+
+# --dump-outputs: elements sampled per parameter tensor (fp32: a 6.7B model's
+# ~390 tensors come to ~6 MB, far under the 64 MB a dump may take)
+DUMP_SAMPLE = 4096
+
+
+def dump_outputs(path, engine, module, lval, write=True):
+    """Write the last timed step's results for an output-for-output comparison
+    of two builds: the loss it returned and a seeded sample of the parameters
+    it left behind (a deferred AdamW is applied first).  Rank 0 writes its own
+    shard; the sample indices depend only on each tensor's position and size."""
+    import numpy as np
+    import torch
+    engine._flush_deferred_update()  # every rank: a ZeRO update gathers
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    if not write:
+        return
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"), np.asarray([lval], dtype=np.float64))
+    parts = []
+    with torch.no_grad():
+        for i, (_, p) in enumerate(module.model.named_parameters()):
+            flat = p.detach().reshape(-1)
+            if flat.numel() > DUMP_SAMPLE:
+                g = torch.Generator()
+                g.manual_seed(977 + i)
+                idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=g)
+                flat = flat[idx.to(flat.device)]
+            parts.append(flat.float().cpu())
+    np.save(os.path.join(path, "params_sample.npy"), torch.cat(parts).numpy())
 
 
 # the engine captures the step after this many eager steps
@@ -210,6 +259,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     lval = engine._reduce_log_loss(loss, 1)
+    peak_mem = torch.cuda.max_memory_allocated() if torch.cuda.is_available() else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, engine, module, lval, write=env.get_rank() == 0)
     tokens = global_batch * S * args.steps
     tps = tokens / elapsed
     fpt = flops_per_token(module.gpt_config, S)
@@ -245,8 +297,7 @@ def main():
                        "dropout": drop, "recompute": recompute},
             "mfu": round(mfu, 4), "tokens_per_gpu": round(tps / n, 1),
             "final_loss": round(lval, 4),
-            "peak_mem_gb": round(torch.cuda.max_memory_allocated() / 2 ** 30, 1)
-            if torch.cuda.is_available() else None,
+            "peak_mem_gb": round(peak_mem / 2 ** 30, 1) if peak_mem is not None else None,
             # forward / data-gradient shapes routed to the MFMA kernel and
             # where each route came from (shipped plan or first-call race);
             # weight gradients follow the kind table (ops/gemm.py)
