@@ -105,46 +105,29 @@ def out_tiles(kind, a, b, t=128):
     return _tiles(a.shape[-1], b.shape[-1], t)
 
 
-# Per-shape routing of the plain data-gradient GEMMs
-# (FLEETX_GEMM_ROUTE=tune, the default; "off" keeps the kind table alone).
-# Which of the MFMA kernel and hipBLASLt is faster depends on the shape
-# (GPT-3 6.7B with the tuned tile order: QKV forward 1466 vs 1331 TF/s, FC1
-# forward 1414 vs 1521; data gradients of QKV / out / FC1 lead, FC2 trails;
-# profiles/r4_gm/).  The first call of a (kind, shape) outside stream capture
-# times both paths (interleaved, a few launches each, on the caller's
-# stream) and the kernel takes the shape only when it wins by ROUTE_MARGIN,
-# so near-ties stay on one side from run to run.  The vendor path of a kind
-# is registered by its caller (VENDOR).
-# Forward GEMMs are not raced: their isolated timing misleads in the step.
-# Beside the forward-overlapped AdamW a gemm5 wave takes its SIMD's whole
-# register file, so the update cannot share those CUs: with the
-# QKV forward on gemm5 (10 % faster alone) the 6.7B step takes 316-317 ms
-# vs 293-295 (three interleaved runs each; ViT-g 461 vs 465 img/s;
-# profiles/r4_route/fwd_race_ab.txt).  Even without the overlapped update
-# (345M in its graph) the race's picks (out-proj, FC2 forward) made the step
-# 0.1-0.3 ms slower (profiles/r4_route/fwd_race_345m.txt).
-ROUTE_TUNE = os.environ.get("FLEETX_GEMM_ROUTE", "tune") == "tune"
-TUNE_KINDS = ("dgrad",)
-# Forward GEMMs follow the plan only (never raced): "plan" = an entry's
-# "route" field; "faster" = also entries without one whose planned kernel time
-# beats the vendor's by ROUTE_MARGIN (lab A/Bs); "off" = hipBLASLt.
-FWD_ROUTE = os.environ.get("FLEETX_GEMM_FWD_ROUTE", "plan")
-ROUTE_MARGIN = 0.03
-VENDOR = {}
-_ROUTE = {}
-_ROUTE_SRC = {}  # key -> "plan" | "race" | "default"
-PLAN_KINDS = ("fwd", "fwd_act", "dgrad", "dgrad_act", "wgrad")
-
 # ----------------------------------------------------------------------------
 # Shipped GEMM plan (reproducible routing; reference parity: the fused path is
 # chosen at config time, ``models/language_model/utils.py:30-36,67-71``).
 # ``gemm_plan_gfx950.json`` (tools/gemm_plan.py: many interleaved launches per
 # candidate on an MI355X) holds, per (kind, dtype, M, N, K) of the model zoo's
 # layer shapes, the route (MFMA kernel or vendor) and the tile-order M-group
-# height.  Shapes in the plan are never raced or re-tuned, so one tree runs the
-# same kernels with the same tile orders on every box and under a profiler;
-# the first-call race / tune remains only for shapes the plan lacks, and not
-# at all under FLEETX_DETERMINISTIC=1 (missing shapes: vendor path, gm 8).
+# height, so one tree runs the same kernels with the same tile orders on
+# every box, on every rank, inside and outside stream capture and under a
+# profiler.  Nothing is timed at run time: a forward or data gradient the plan
+# does not route runs on hipBLASLt.
+# Which of the two is faster depends on the shape (GPT-3 6.7B with the tuned
+# tile order: QKV forward 1466 vs 1331 TF/s, FC1 forward 1414 vs 1521; data
+# gradients of QKV / out / FC1 lead, FC2 trails; profiles/r4_gm/), so the tool
+# writes a data gradient's route when the kernel wins by 3 %.
+# Forward routes are written by hand (tools/gemm_plan.py --fwd-route) after a
+# step A/B: their isolated timing misleads in the step.  Beside the
+# forward-overlapped AdamW a gemm5 wave takes its SIMD's whole register file,
+# so the update cannot share those CUs: with the QKV forward on gemm5 (10 %
+# faster alone) the 6.7B step takes 316-317 ms vs 293-295 (three interleaved
+# runs each; ViT-g 461 vs 465 img/s; the forward A/B in profiles/r4_route/).
+# Even without the overlapped update (345M in its graph) the isolated winners
+# (out-proj, FC2 forward) made the step 0.1-0.3 ms slower (the 345M A/B in
+# profiles/r4_route/).  The shipped plan routes no forward.
 # Key convention: M = rows of the activation (tokens), N = output columns,
 # K = reduction; wgrad: M = tokens, N = out features, K = in features.
 # ----------------------------------------------------------------------------
@@ -152,6 +135,7 @@ PLAN_FILE = os.environ.get("FLEETX_GEMM_PLAN",
                            os.path.join(os.path.dirname(os.path.abspath(__file__)),
                                         "gemm_plan_gfx950.json"))
 _PLAN = None  # {(kind, dtype, M, N, K): entry}
+_ROUTE = {}   # (kind, M, N, K, dtype) -> (kernel?, "plan" | "default"), per loaded plan
 
 
 def _deterministic():
@@ -171,39 +155,12 @@ def kernel_shape(kind, M, N, K):
     return la, lb, f32, M, N, K
 
 
-# Vendor-GEMM solutions (hipBLASLt / rocBLAS, the forward and TN data-gradient
-# GEMMs that stay on the library) picked per shape by PyTorch TunableOp on an
-# MI355X for the single-GPU model zoo (scripts/gpu_r5_ar.sh).  Loaded read-only:
-# shapes missing from the file run the library default.
-# Opt-in (FLEETX_VENDOR_TUNE=on): its A/B is neutral at the 6.7B headline
-# (288.17 vs 288.16 ms, profiles/r5_vendor_tune/) and it turns TunableOp on
-# for every torch GEMM of the process; PYTORCH_TUNABLEOP_* set by the user win.
-VENDOR_TUNE_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)),
-                                "tunableop_gfx950.csv")
-
-
-def enable_vendor_tuning():
-    if os.environ.get("FLEETX_VENDOR_TUNE", "off") != "on" \
-            or any(k.startswith("PYTORCH_TUNABLEOP") for k in os.environ) \
-            or not torch.cuda.is_available() or not os.path.exists(VENDOR_TUNE_FILE):
-        return False
-    import torch.cuda.tunable as tunable
-    tunable.enable(True)
-    tunable.tuning_enable(False)
-    tunable.record_untuned_enable(False)
-    if not tunable.read_file(VENDOR_TUNE_FILE):
-        tunable.enable(False)
-        return False
-    return True
-
-
 def load_plan(path=None, force=False):
     """Read the plan (once) and preload its tile orders into the kernel
     library; returns {key: entry}.  A missing / foreign-arch plan is empty."""
     global _PLAN
     if _PLAN is not None and not force:
         return _PLAN
-    enable_vendor_tuning()
     import json
     plan = {}
     path = path or PLAN_FILE
@@ -222,6 +179,7 @@ def load_plan(path=None, force=False):
             key = (e["kind"], e.get("dtype", "bf16"), int(e["M"]), int(e["N"]), int(e["K"]))
             plan[key] = e
     _PLAN = plan
+    _ROUTE.clear()
     if plan and _lib.available() and torch.cuda.is_available():
         k = _lib.kernels()
         for (kind, dt, M, N, K), e in plan.items():
@@ -232,17 +190,12 @@ def load_plan(path=None, force=False):
     return plan
 
 
-def _dt_name(dtype):
-    return "bf16" if dtype == torch.bfloat16 else "fp16"
-
-
-def _plan_entry(kind, dtype, M, N, K):
+def _plan_entry(plan, kind, dtype, M, N, K):
     """The plan entry of a shape; fp16 shapes the plan lacks take the bf16
     entry (same kernels, same MFMA cycle counts, same tile orders: the fp16
-    O2 step otherwise raced the QKV data gradient onto hipBLASLt plus a
+    O2 step otherwise put the QKV data gradient on hipBLASLt plus a
     transpose, +16 ms per 6.7B step, profiles/r6_fp16/)."""
-    plan = load_plan()
-    e = plan.get((kind, _dt_name(dtype), M, N, K))
+    e = plan.get((kind, "bf16" if dtype == torch.bfloat16 else "fp16", M, N, K))
     if e is None and dtype == torch.float16:
         e = plan.get((kind, "bf16", M, N, K))
     return e
@@ -250,123 +203,68 @@ def _plan_entry(kind, dtype, M, N, K):
 
 def plan_route(kind, M, N, K, dtype):
     """True / False when the plan fixes the route of this shape, else None."""
-    e = _plan_entry(kind, dtype, M, N, K)
+    e = _plan_entry(load_plan(), kind, dtype, M, N, K)
     if e is None or "route" not in e:
         return None
     return e["route"] == "kernel"
 
 
+def route(mode, auto_kinds, plan, kind, dtype, M, N, K):
+    """(MFMA kernel?, source) of one GEMM, from its arguments alone: the mode,
+    then the kind table (output tiles against ``MIN_TILES``; the plan is not
+    consulted), then the plan's ``route`` of a forward / data gradient, else
+    the vendor library."""
+    if mode != "auto":
+        return mode != "blas", "mode"
+    if kind in auto_kinds:
+        if kind == "wgrad":
+            return _tiles(N, K) >= WGRAD_MIN_TILES, "kind"
+        return _tiles(M, N) >= MIN_TILES, "kind"
+    if kind in ("fwd", "dgrad"):
+        e = _plan_entry(plan, kind, dtype, M, N, K)
+        if e is not None and "route" in e:
+            return e["route"] == "kernel", "plan"
+    return False, "default"
+
+
 def route_table():
-    """{(kind, M, N, K): True if the MFMA kernel takes it} decided so far."""
-    return {k[:4]: v for k, v in _ROUTE.items()}
+    """{(kind, M, N, K): True if the MFMA kernel takes it} of the forwards and
+    data gradients the plan (or its silence) has decided so far."""
+    return {k[:4]: v[0] for k, v in _ROUTE.items()}
 
 
 def kernel_routes():
-    """{"kind MxNxK": source} of every shape routed to the MFMA kernel so far
-    (data gradients: "plan" / "race"; forwards: "plan"), for the bench line."""
-    out = {}
-    for k, v in _ROUTE.items():
-        if v:
-            out["%s %dx%dx%d" % k[:4]] = _ROUTE_SRC.get(k, "default")
-    for k, v in _FWD_ROUTE.items():
-        if v:
-            out["%s %dx%dx%d" % k[:4]] = "plan"
-    return dict(sorted(out.items()))
-
-
-def route_sources():
-    """{"plan": n, "race": n, "default": n}: where the routes came from."""
-    out = {"plan": 0, "race": 0, "default": 0}
-    for v in _ROUTE_SRC.values():
-        out[v] += 1
-    return out
-
-
-def _race(f_hip, f_vendor, iters=3):
-    if f_hip() is None:
-        return False
-    f_vendor()
-    t = []
-    for f in (f_hip, f_vendor, f_hip, f_vendor):
-        e0 = torch.cuda.Event(enable_timing=True)
-        e1 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            f()
-        e1.record()
-        e1.synchronize()
-        t.append(e0.elapsed_time(e1))
-    return min(t[0], t[2]) < (1.0 - ROUTE_MARGIN) * min(t[1], t[3])
-
-
-def _tuned_route(kind, a, b):
-    a2 = a.reshape(-1, a.shape[-1])
-    M = a2.shape[0]
-    if kind == "fwd":
-        N, K = b.shape[0], b.shape[1]
-    else:
-        N, K = b.shape[1], b.shape[0]
-    key = (kind, M, N, K, a.dtype)
-    r = _ROUTE.get(key)
-    if r is not None:
-        return r
-    p = plan_route(kind, M, N, K, a.dtype)
-    if p is not None:
-        _ROUTE[key], _ROUTE_SRC[key] = p and _ok(a2, b), "plan"
-        return _ROUTE[key]
-    if out_tiles(kind, a, b) < MIN_TILES or kind not in VENDOR or not _ok(a2, b) \
-            or _deterministic():
-        _ROUTE[key], _ROUTE_SRC[key] = False, "default"
-        return False
-    if torch.cuda.is_current_stream_capturing():
-        return False
-    if kind == "fwd":
-        r = _race(lambda: linear_fwd(a2, b), lambda: VENDOR["fwd"](a2, b))
-    else:
-        r = _race(lambda: linear_dgrad(a2, b), lambda: VENDOR["dgrad"](a2, b))
-    _ROUTE[key], _ROUTE_SRC[key] = r, "race"
-    return r
-
-
-_FWD_ROUTE = {}  # forward routes from the plan (kept apart from the raced table)
-
-
-def _planned_fwd_route(a, b):
-    key = ("fwd", a.numel() // a.shape[-1], b.shape[0], b.shape[1], a.dtype)
-    r = _FWD_ROUTE.get(key)
-    if r is not None:
-        return r
-    e = _plan_entry("fwd", a.dtype, *key[1:4])
-    r = False
-    if e is not None:
-        if "route" in e:
-            r = e["route"] == "kernel"
-        elif FWD_ROUTE == "faster" and e.get("vendor_ms") and e.get("kernel_ms"):
-            r = e["kernel_ms"] < (1.0 - ROUTE_MARGIN) * e["vendor_ms"]
-        r = r and _ok(a.reshape(-1, a.shape[-1]), b)
-    _FWD_ROUTE[key] = r
-    return r
+    """{"kind MxNxK": "plan"} of every forward / data-gradient shape routed to
+    the MFMA kernel so far, for the bench line."""
+    return dict(sorted(("%s %dx%dx%d" % k[:4], v[1]) for k, v in _ROUTE.items() if v[0]))
 
 
 def use(kind, a, b=None):
     """Whether GEMM ``kind`` ('fwd' | 'fwd_act' | 'dgrad' | 'dgrad_act' |
     'wgrad'; ``_act`` = with the GeLU / GeLU' epilogue) on these operands goes
     to the MFMA kernel (the kernel itself may still decline the shape)."""
-    if _MODE == "blas" or not a.is_cuda or a.dtype not in (torch.bfloat16, torch.float16):
+    if not a.is_cuda or a.dtype not in (torch.bfloat16, torch.float16):
         return False
-    if _MODE == "auto":
-        if b is None:
-            return False
-        if kind in PLAN_KINDS and (kind in TUNE_KINDS or kind in AUTO_KINDS):
-            load_plan()
-        if kind in AUTO_KINDS:
-            return out_tiles(kind, a, b) >= (WGRAD_MIN_TILES if kind == "wgrad" else MIN_TILES)
-        if ROUTE_TUNE and kind in TUNE_KINDS:
-            return _tuned_route(kind, a, b)
-        if kind == "fwd" and FWD_ROUTE != "off":
-            return _planned_fwd_route(a, b)
+    if _MODE != "auto":
+        return _MODE != "blas"
+    if b is None:
         return False
-    return True
+    M = a.numel() // a.shape[-1]
+    if kind.startswith("fwd"):
+        N, K = b.shape[0], b.shape[1]
+    elif kind.startswith("dgrad"):
+        N, K = b.shape[1], b.shape[0]
+    else:
+        N, K = a.shape[-1], b.shape[-1]
+    plan = load_plan()  # also preloads the tile orders before a first launch
+    key = (kind, M, N, K, a.dtype)
+    # only what the plan decides is cached: the kind table may change under it
+    r = _ROUTE.get(key) if kind not in AUTO_KINDS else None
+    if r is None:
+        r = route(_MODE, AUTO_KINDS, plan, kind, a.dtype, M, N, K)
+        if kind in ("fwd", "dgrad") and r[1] != "kind":
+            _ROUTE[key] = r
+    return r[0]
 
 
 def _ok(*ts):

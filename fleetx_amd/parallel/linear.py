@@ -1,10 +1,13 @@
 """Linear layers on the hand-written gfx950 GEMM (``ops.gemm``), with the
 weight-gradient GEMM accumulating straight into the fp32 ``main_grad`` buffer.
 
-GEMM routing: every forward / data-gradient / weight-gradient GEMM first tries
-the MFMA kernel in its native operand layout (no transposed copies), with the
-bias, GeLU and GeLU-derivative fused into its epilogue (``fused_mlp``); shapes
-it does not cover (or ``FLEETX_GEMM=blas``) take the hipBLASLt paths below.
+GEMM routing (``ops.gemm.use``, default ``FLEETX_GEMM=auto``): weight
+gradients go to the MFMA kernel by the kind table (shapes of enough output
+tiles), in their native token-major layout; data gradients and forwards go
+there only where the shipped plan routes their shape (today most data
+gradients, no forward); everything else, and any call the kernel declines,
+takes the hipBLASLt paths below with their TN transposes.  The GeLU / GeLU'
+epilogues (``fused_mlp``) are opt-in kinds of the table.
 
 Without this, every weight gradient goes hipBLASLt (bf16 dW) -> autograd
 ``.grad`` -> a post-accumulate hook that adds it into the fp32 flat buffer:
@@ -58,10 +61,6 @@ def dgrad(dy, w):
         from ..ops.elementwise import transpose2d
         return F.linear(dy, transpose2d(w))
     return torch.matmul(dy, w)
-
-
-G.VENDOR["dgrad"] = dgrad
-G.VENDOR["fwd"] = F.linear
 
 
 def _fused(p):

@@ -32,18 +32,30 @@ def test_gemm_routing_table():
     def t(*shape):  # a shape-only stand-in for a bf16 GPU tensor
         return NS(shape=shape, numel=lambda: __import__("math").prod(shape), is_cuda=True,
                   dtype=torch.bfloat16)
-    old = G._MODE, G.ROUTE_TUNE
+    old = G._MODE, set(G.AUTO_KINDS)
     try:
         G.set_mode("auto")
-        G.ROUTE_TUNE = False
+        G.set_auto_kinds("wgrad")
+        G.load_plan(G.PLAN_FILE, force=True)
         x, w_qkv = t(8192, 4096), t(12288, 4096)
         # 6.7B: weight gradients and the fused-epilogue GEMMs go to the MFMA kernel
         assert G.out_tiles("wgrad", t(8192, 12288), x, 256) == 48 * 16
         assert G.use("wgrad", t(8192, 12288), x) and G.use("wgrad", t(8192, 4096), x)
         assert not G.use("fwd_act", x, t(16384, 4096))          # opt-in (FLEETX_GEMM_AUTO)
-        # forward and data-gradient GEMMs are not in the kind table (the
-        # per-shape race decides them on GPU; off here)
-        assert not G.use("fwd", x, w_qkv) and not G.use("dgrad", t(8192, 12288), w_qkv)
+        # forward and data-gradient GEMMs are not in the kind table: the
+        # shipped plan decides them.  6.7B: the QKV data gradient on the
+        # kernel, out / FC1 / FC2 on the vendor library, as every forward
+        w_out, w_fc1, w_fc2 = t(4096, 4096), t(16384, 4096), t(4096, 16384)
+        assert G.use("dgrad", t(8192, 12288), w_qkv)
+        assert not G.use("dgrad", x, w_out) and not G.use("dgrad", t(8192, 16384), w_fc1)
+        assert not G.use("dgrad", x, w_fc2)
+        plan = G.load_plan()
+        for n, k in ((4096, 12288), (4096, 4096), (4096, 16384), (16384, 4096)):
+            r = G.route("auto", {"wgrad"}, plan, "dgrad", torch.bfloat16, 8192, n, k)
+            assert r == (n == 4096 and k == 12288, "plan")
+        assert not G.use("fwd", x, w_qkv) and not G.use("fwd", x, w_out)
+        assert not G.use("fwd", x, w_fc1) and not G.use("fwd", t(8192, 16384), w_fc2)
+        assert G.kernel_routes() == {"dgrad 8192x4096x12288": "plan"}
         # hidden 1024-2048 shapes run on 128 x 128 tiles: 1.3B out-proj (256
         # tiles), 345M qkv / fc1 (192 / 256); the 345M out-proj (64 tiles) runs
         # split along K (gemm5.hip g5_split_plan); 32 tiles stay on hipBLASLt
@@ -55,7 +67,8 @@ def test_gemm_routing_table():
         assert not G.use("wgrad", t(8192, 12288), x)
     finally:
         G.set_mode(old[0])
-        G.ROUTE_TUNE = old[1]
+        G.set_auto_kinds(old[1])
+        G.load_plan(force=True)
 
 
 def test_decode_split_rule():

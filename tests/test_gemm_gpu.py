@@ -242,37 +242,56 @@ def test_tile_order_autotune_is_bitwise_neutral(gemm):
     assert (1, 1, 1, N, K, M) in tuned and tuned[(1, 1, 1, N, K, M)] in (1, 2, 4, 8, 16)
 
 
-def test_route_tuner_picks_a_path_and_both_agree():
-    """Per-shape routing of plain data-gradient GEMMs (ops/gemm.py
-    _tuned_route): the first call of a shape races the MFMA kernel against the
-    registered vendor path, caches the winner, and either path matches fp32."""
+def test_plan_routes_the_data_gradient_and_both_paths_agree(tmp_path):
+    """Routing of plain data-gradient GEMMs (ops/gemm.py route): the plan
+    entry's route picks the MFMA kernel or the vendor path, a shape without an
+    entry takes the vendor path, and either path matches fp32."""
+    import json
     from fleetx_amd.ops import gemm as G
     from fleetx_amd.parallel import linear as L
-    old = (G._MODE, G.ROUTE_TUNE, set(G.AUTO_KINDS))
+    old = (G._MODE, set(G.AUTO_KINDS))
+    M, N, K = 4096, 6144, 1024
+
+    def plan(route):
+        entries = [] if route is None else [
+            {"kind": "dgrad", "dtype": "bf16", "M": M, "N": K, "K": N, "route": route}]
+        p = tmp_path / "plan.json"
+        p.write_text(json.dumps({"arch": "gfx950", "entries": entries}))
+        G.load_plan(str(p), force=True)
+
     try:
         G.set_mode("auto")
-        G.ROUTE_TUNE = True
         G.set_auto_kinds("wgrad")
         torch.manual_seed(12)
-        M, N, K = 4096, 6144, 1024
         x = torch.randn(M, K, device="cuda", dtype=torch.bfloat16)
         w = torch.randn(N, K, device="cuda", dtype=torch.bfloat16) * 0.05
         dy = torch.randn(M, N, device="cuda", dtype=torch.bfloat16)
-        y = L.fwd_gemm(x, w)
-        dx = L.dgrad_gemm(dy, w)
-        table = G.route_table()
-        # data gradients race; forward GEMMs do not (see ops/gemm.py)
-        assert ("dgrad", M, K, N) in table and ("fwd", M, N, K) not in table
-        assert _rel(y, x.float() @ w.float().t()) < 1e-2
-        assert _rel(dx, dy.float() @ w.float()) < 1e-2
-        # small outputs never race (under MIN_TILES): vendor path, cached False
         dys = torch.randn(256, 512, device="cuda", dtype=torch.bfloat16)
-        L.dgrad_gemm(dys, w[:512])
-        assert G.route_table()[("dgrad", 256, K, 512)] is False
+        ref_y, ref_dx = x.float() @ w.float().t(), dy.float() @ w.float()
+        for route, same_as in (("kernel", lambda: G.linear_dgrad(dy, w)),
+                               ("vendor", lambda: L.dgrad(dy, w)),
+                               (None, lambda: L.dgrad(dy, w))):
+            plan(route)
+            y = L.fwd_gemm(x, w)
+            dx = L.dgrad_gemm(dy, w)
+            table = G.route_table()
+            assert table[("dgrad", M, K, N)] is (route == "kernel")
+            assert table[("fwd", M, N, K)] is False    # no forward entry: vendor
+            assert torch.equal(dx, same_as())
+            assert _rel(y, ref_y) < 1e-2
+            assert _rel(dx, ref_dx) < 1e-2
+            # a small output without an entry: vendor path
+            L.dgrad_gemm(dys, w[:512])
+            assert G.route_table()[("dgrad", 256, K, 512)] is False
+            # nothing is decided by the call: a second one leaves the same table
+            table = G.route_table()
+            assert torch.equal(L.dgrad_gemm(dy, w), dx)
+            L.fwd_gemm(x, w)
+            assert G.route_table() == table
     finally:
         G.set_mode(old[0])
-        G.ROUTE_TUNE = old[1]
-        G.set_auto_kinds(old[2])
+        G.set_auto_kinds(old[1])
+        G.load_plan(force=True)
 
 
 @pytest.mark.parametrize("nf,split", [(4, 1), (4, 3), (8, 2), (8, 1)])

@@ -1,20 +1,24 @@
 """Generate the shipped GEMM plan (``fleetx_amd/ops/gemm_plan_gfx950.json``).
 
-For every transformer-layer shape of the model zoo (GPT 345M / 1.3B / 6.7B,
-the 6.7B tensor-parallel shards of BASELINE config 3, ViT-g/14) and every GEMM
-kind of a linear layer (forward, data gradient, fp32 weight gradient), this
-times the MFMA kernel at each tile-order M-group height and the vendor path,
-in interleaved rounds of back-to-back launches, and keeps the median of each
-candidate.  The plan then fixes, per shape, the tile order and (for the data
-gradient) the route, so a run never decides them from a first-call race on a
-noisy box (``ops/gemm.py load_plan``).
+For every linear-layer shape of the model zoo (GPT 345M / 1.3B / 6.7B with
+their LM heads, the 6.7B tensor-parallel shards of BASELINE config 3,
+ViT-g/14) and every GEMM kind of a linear layer (forward, data gradient, fp32
+weight gradient), this times the MFMA kernel at each tile-order M-group height
+and the vendor path, in interleaved rounds of back-to-back launches, and keeps
+the median of each candidate.  The plan then fixes, per shape, the tile order
+and (for the data gradient) the route; a run decides neither
+(``ops/gemm.py route``), and a shape the plan lacks runs on the vendor library.
 
 Forward routes are not decided here: in the training step the forward GEMMs
 share the chip with the forward-overlapped AdamW, which an isolated timing
 cannot see (``tools/bench_gemm_beside_adamw.py``); ``--fwd-route kernel``
 writes them explicitly after a step A/B.
 
-    python tools/gemm_plan.py [--models 6.7B,1.3B,345M,vitg,6.7B-tp2] [--out plan.json]
+``--merge`` measures only the keys the plan at ``--out`` lacks and appends
+them; the entries it already has are written back untouched, so a new layer
+never re-decides an old route.
+
+    python tools/gemm_plan.py [--models 6.7B,1.3B,345M,vitg,6.7B-tp2] [--out plan.json] [--merge]
 """
 import argparse
 import json
@@ -27,14 +31,15 @@ sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..")
 
 import torch  # noqa: E402
 
+VOCAB = 50304  # what bench.py builds the GPT models with
 # name: (tokens, [(layer, in, out), ...])
 MODELS = {
     "345M": (8192, [("qkv", 1024, 3072), ("out", 1024, 1024), ("fc1", 1024, 4096),
-                    ("fc2", 4096, 1024)]),
+                    ("fc2", 4096, 1024), ("lm_head", 1024, VOCAB)]),
     "1.3B": (8192, [("qkv", 2048, 6144), ("out", 2048, 2048), ("fc1", 2048, 8192),
-                    ("fc2", 8192, 2048)]),
+                    ("fc2", 8192, 2048), ("lm_head", 2048, VOCAB)]),
     "6.7B": (8192, [("qkv", 4096, 12288), ("out", 4096, 4096), ("fc1", 4096, 16384),
-                    ("fc2", 16384, 4096)]),
+                    ("fc2", 16384, 4096), ("lm_head", 4096, VOCAB)]),
     # BASELINE config 3 family: TP2 shards, micro-batch 4 (N=4/8) and 8 (N=2)
     "6.7B-tp2": (4096, [("qkv", 4096, 6144), ("out", 2048, 4096), ("fc1", 4096, 8192),
                         ("fc2", 8192, 4096)]),
@@ -76,36 +81,45 @@ def main():
     ap.add_argument("--margin", type=float, default=0.03)
     ap.add_argument("--fwd-route", default="", choices=["", "kernel", "vendor"])
     ap.add_argument("--dtypes", default="bf16")
+    ap.add_argument("--merge", action="store_true",
+                    help="keep the entries of the plan at --out as they are and measure "
+                         "only the keys it lacks")
     a = ap.parse_args()
     from fleetx_amd.ops import _lib
     from fleetx_amd.ops import gemm as G
-    from fleetx_amd.parallel import linear as L  # registers the vendor paths  # noqa: F401
+    from fleetx_amd.parallel import linear as L
+    import torch.nn.functional as F
     k = _lib.kernels()
     k.gemm_set_tune(0)
     G.set_mode("hip")
     dev = "cuda"
     entries, seen = [], set()
+    if a.merge:
+        with open(a.out) as f:
+            entries = json.load(f)["entries"]
+        seen = {(e["kind"], e["dtype"], e["M"], e["N"], e["K"]) for e in entries}
     t0 = time.time()
     for dtn in a.dtypes.split(","):
         dt = torch.bfloat16 if dtn == "bf16" else torch.float16
         for model in a.models.split(","):
             M, layers = MODELS[model]
             for lname, kin, kout in layers:
+                # kind: plan key (M, N, K)
+                keys = {"fwd": (M, kout, kin), "dgrad": (M, kin, kout), "wgrad": (M, kout, kin)}
+                keys = {kind: key for kind, key in keys.items() if (kind, dtn) + key not in seen}
+                if not keys:
+                    continue
                 x = torch.randn(M, kin, device=dev, dtype=dt)
                 w = torch.randn(kout, kin, device=dev, dtype=dt) * 0.02
                 dy = torch.randn(M, kout, device=dev, dtype=dt)
                 dw = torch.empty(kout, kin, device=dev, dtype=torch.float32)
-                kinds = {
-                    # kind: (plan key (M, N, K), kernel fn, vendor fn)
-                    "fwd": ((M, kout, kin), lambda: G.linear_fwd(x, w), lambda: G.VENDOR["fwd"](x, w)),
-                    "dgrad": ((M, kin, kout), lambda: G.linear_dgrad(dy, w),
-                              lambda: G.VENDOR["dgrad"](dy, w)),
-                    "wgrad": ((M, kout, kin), lambda: G.linear_wgrad(dy, x, dw, False), None),
-                }
-                for kind, (key, fk, fv) in kinds.items():
-                    if (kind, dtn) + key in seen:
-                        continue
+                # kind: (kernel fn, vendor fn)
+                fns_of = {"fwd": (lambda: G.linear_fwd(x, w), lambda: F.linear(x, w)),
+                          "dgrad": (lambda: G.linear_dgrad(dy, w), lambda: L.dgrad(dy, w)),
+                          "wgrad": (lambda: G.linear_wgrad(dy, x, dw, False), None)}
+                for kind, key in keys.items():
                     seen.add((kind, dtn) + key)
+                    fk, fv = fns_of[kind]
                     fns = {}
                     for g in GMS:
                         fns["gm%d" % g] = (lambda g=g, fk=fk: (k.gemm_set_gm(g), fk()))

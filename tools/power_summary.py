@@ -1,6 +1,6 @@
 """Summarise `amd-smi metric -p -c --json` samples (concatenated JSON
 documents, one per sample): socket power and the mean / min / max gfx clock
-over the XCDs.  Used by scripts/gpu_r6_al.sh (power and clocks during a step).
+over the XCDs (power and clocks during a step: ``profiles/r6_power/``).
 
     python tools/power_summary.py [--min-power W] samples.jsonl [more.jsonl ...]
 
