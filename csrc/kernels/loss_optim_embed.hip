@@ -39,8 +39,12 @@ __global__ __launch_bounds__(256) void ce_stats_kernel(
       s *= __expf(m - lm);
       m = lm;
     }
+    // m still -inf: all 8 are -inf (masked vocabulary) and add nothing;
+    // exp(-inf - -inf) would be NaN
+    if (m != -INFINITY) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) s += __expf(a[j] - m);
+      for (int j = 0; j < 8; ++j) s += __expf(a[j] - m);
+    }
   }
   for (int c = nv * 8 + threadIdx.x; c < V; c += 256) {
     float a = Elt<T>::to_f(x[c]);
@@ -48,7 +52,7 @@ __global__ __launch_bounds__(256) void ce_stats_kernel(
       s *= __expf(m - a);
       m = a;
     }
-    s += __expf(a - m);
+    if (m != -INFINITY) s += __expf(a - m);
   }
   // block reduce (max, sum)
   __shared__ float sm[4], ss[4];
@@ -75,7 +79,8 @@ __global__ __launch_bounds__(256) void ce_stats_kernel(
   }
 }
 
-// dlogits = (softmax - onehot) * g[row], written in place (or to dx).
+// dlogits = (softmax - onehot) * g[row], written in place (or to dx); a row
+// whose label is ignore_index gets exactly 0 whatever g[row] holds.
 template <typename T>
 __global__ __launch_bounds__(256) void ce_bwd_kernel(const uint16_t* __restrict__ logits,
                                                      uint16_t* __restrict__ dx,
@@ -89,7 +94,8 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const uint16_t* __restrict_
   const float L = lse[row];
   const float gr = g[row];
   const long lab = labels[row];
-  const long local = (lab == ignore_index) ? -1 : lab - vocab_start;
+  const bool ignored = lab == ignore_index;
+  const long local = ignored ? -1 : lab - vocab_start;
   const int nv = V / 8;
   for (int v = threadIdx.x; v < nv; v += 256) {
     float a[8];
@@ -98,14 +104,14 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const uint16_t* __restrict_
     for (int j = 0; j < 8; ++j) {
       float p = __expf(a[j] - L);
       if (v * 8 + j == local) p -= 1.f;
-      a[j] = p * gr;
+      a[j] = ignored ? 0.f : p * gr;
     }
     store8<T>(d + v * 8, a);
   }
   for (int c = nv * 8 + threadIdx.x; c < V; c += 256) {
     float p = __expf(Elt<T>::to_f(x[c]) - L);
     if (c == local) p -= 1.f;
-    d[c] = Elt<T>::from_f(p * gr);
+    d[c] = Elt<T>::from_f(ignored ? 0.f : p * gr);
   }
 }
 

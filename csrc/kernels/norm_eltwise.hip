@@ -917,9 +917,10 @@ __global__ __launch_bounds__(256) void dropout_bwd_colsum_kernel(
 // Plain dropout (embedding / generic): y = dropout(x)
 template <typename T>
 __global__ __launch_bounds__(256) void dropout_fwd_kernel(const uint16_t* __restrict__ x,
-                                                          uint16_t* __restrict__ y, long n8,
+                                                          uint16_t* __restrict__ y, long n,
                                                           DropCfg drop_) {
   const DropCfg drop = resolve_drop(drop_);
+  const long n8 = n / 8;
   for (long v = blockIdx.x * (long)blockDim.x + threadIdx.x; v < n8; v += (long)gridDim.x * blockDim.x) {
     const long off = v * 8;
     float a[8];
@@ -927,6 +928,10 @@ __global__ __launch_bounds__(256) void dropout_fwd_kernel(const uint16_t* __rest
     drop_apply8(a, (uint64_t)off, drop);
     store8<T>(y + off, a);
   }
+  // scalar tail: the last n % 8 elements of a flat tensor
+  for (long i = n8 * 8 + blockIdx.x * (long)blockDim.x + threadIdx.x; i < n;
+       i += (long)gridDim.x * blockDim.x)
+    y[i] = Elt<T>::from_f(drop_apply(Elt<T>::to_f(x[i]), (uint64_t)i, drop));
 }
 
 DropCfg make_drop(float p, uint64_t key) {
@@ -1231,7 +1236,7 @@ extern "C" void fx_dropout_fwd(int dtype, const void* x, void* y, long n, float 
   DropCfg d = make_drop(p, key);
   long n8 = n / 8;
   FX_DISPATCH_T(dtype, dropout_fwd_kernel<T><<<grid_for(n8), 256, 0, st>>>(
-                           (const uint16_t*)x, (uint16_t*)y, n8, d));
+                           (const uint16_t*)x, (uint16_t*)y, n, d));
 }
 
 // graph-mode dropout salt (see resolve_drop): a device uint64 read by every

@@ -4,6 +4,9 @@ GPU tensors ALWAYS go through the HIP kernels: if the extension is missing
 on a GPU box the op raises (no silent eager fallback).  CPU tensors use the
 PyTorch reference math in each op module (same RNG hash, same formulas) --
 that path exists for the CPU test-suite and the CPU float32 plumbing config.
+The one exception on the GPU is a shape the vector kernels cannot address
+(``vec8_ok``: row width not a multiple of 8, or a buffer off a 16-byte
+boundary): it takes the same formula branch instead of writing out of bounds.
 """
 import os
 
@@ -65,6 +68,21 @@ def ptr(t):
 
 def on_gpu(t):
     return t is not None and t.is_cuda
+
+
+def vec8_ok(width, *ts):
+    """True when the 16-byte-vector kernels can take these tensors: all on
+    the GPU, row width a multiple of 8 elements, every buffer 16-byte aligned
+    (``None`` entries are skipped).  Anything else -- CPU tensors, a ragged
+    width, a view that starts off a 16-byte boundary -- is computed by the
+    op's PyTorch formula branch, which runs on either device
+    (docs/KERNELS.md, "Design rules")."""
+    if width % 8:
+        return False
+    for t in ts:
+        if t is not None and (not t.is_cuda or t.data_ptr() % 16):
+            return False
+    return True
 
 
 def check_contig(*ts):

@@ -34,7 +34,7 @@ class _BiasGelu(torch.autograd.Function):
         ctx.has_bias = bias is not None
         x = x.contiguous()
         cols = x.shape[-1]
-        if x.is_cuda:
+        if _lib.vec8_ok(cols, x, bias):
             y = torch.empty_like(x)
             _lib.kernels().bias_gelu_fwd(_lib.dt_code(x.dtype), int(erf), x.data_ptr(),
                                          _lib.ptr(bias), y.data_ptr(), x.numel(), cols,
@@ -51,7 +51,7 @@ class _BiasGelu(torch.autograd.Function):
         dy = dy.contiguous()
         cols = x.shape[-1]
         rows = x.numel() // cols
-        if dy.is_cuda:
+        if _lib.vec8_ok(cols, dy, x, bias):
             k = _lib.kernels()
             splits = k.coltile_splits(rows, cols)
             part = torch.empty(splits, cols, device=x.device, dtype=torch.float32)
@@ -80,7 +80,7 @@ def bias_gelu(x, bias=None, approximate=True):
 def gelu_plain(h, erf=False):
     """``gelu(h)`` without autograd (fallback half of the fused FC1 epilogue)."""
     h = h.contiguous()
-    if h.is_cuda:
+    if _lib.vec8_ok(h.shape[-1], h):
         y = torch.empty_like(h)
         _lib.kernels().bias_gelu_fwd(_lib.dt_code(h.dtype), int(erf), h.data_ptr(), 0,
                                      y.data_ptr(), h.numel(), h.shape[-1], _lib.stream())
@@ -94,7 +94,7 @@ def gelu_grad(dy, h, erf=False, colsum=None):
     result (a bias gradient) from the same pass."""
     dy = dy.contiguous()
     h = h.contiguous()
-    if dy.is_cuda:
+    if _lib.vec8_ok(h.shape[-1], dy, h):
         k = _lib.kernels()
         cols = h.shape[-1]
         rows = h.numel() // cols
@@ -128,18 +128,21 @@ class _BiasDropoutAdd(torch.autograd.Function):
         x = x.contiguous()
         cols = x.shape[-1]
         ctx.cols = cols
-        if x.is_cuda:
+        if residual is not None:
+            residual = residual.contiguous()
+        if _lib.vec8_ok(cols, x, bias, residual):
             out = torch.empty_like(x)
-            if residual is not None:
-                residual = residual.contiguous()
             _lib.kernels().bias_dropout_add_fwd(_lib.dt_code(x.dtype), x.data_ptr(),
                                                 _lib.ptr(bias), _lib.ptr(residual),
                                                 out.data_ptr(), x.numel(), cols, float(p), key,
                                                 _lib.stream())
         else:
-            v = x if bias is None else x + bias
+            # fp32 like the kernel: one rounding, at the store
+            v = x.float() if bias is None else x.float() + bias.float()
             v = _dropout_ref(v, p, key)
-            out = v + residual if residual is not None else v
+            if residual is not None:
+                v = v + residual.float()
+            out = v.to(x.dtype)
         return out
 
     @staticmethod
@@ -148,7 +151,10 @@ class _BiasDropoutAdd(torch.autograd.Function):
         cols = ctx.cols
         rows = dout.numel() // cols
         dres = dout if ctx.has_res else None
-        if dout.is_cuda:
+        bias = ctx.bias
+        fused = dout.is_cuda and bias is not None and getattr(bias, "_fx_fused_wgrad", False) \
+            and hasattr(bias, "main_grad")
+        if _lib.vec8_ok(cols, dout):
             k = _lib.kernels()
             dc = _lib.dt_code(dout.dtype)
             st = _lib.stream()
@@ -158,9 +164,6 @@ class _BiasDropoutAdd(torch.autograd.Function):
                 splits = k.coltile_splits(rows, cols)
                 part = torch.empty(splits, cols, device=dout.device, dtype=torch.float32)
                 from .norm import colsum_tickets
-                bias = ctx.bias
-                fused = bias is not None and getattr(bias, "_fx_fused_wgrad", False) \
-                    and hasattr(bias, "main_grad")
                 if fused:  # fp32 bias gradient straight into main_grad
                     fin = {"out_f32": bias.main_grad.data_ptr(),
                            "acc": int(not getattr(bias, "_fx_fresh", False))}
@@ -179,7 +182,14 @@ class _BiasDropoutAdd(torch.autograd.Function):
                               ctx.key, st)
         else:
             dx = _dropout_ref(dout, ctx.p, ctx.key)
-            db = dx.float().reshape(rows, cols).sum(0).to(dout.dtype) if ctx.has_bias else None
+            db = None
+            if ctx.has_bias:
+                s = dx.float().reshape(rows, cols).sum(0)
+                if fused:
+                    from .norm import _into_main_grad
+                    _into_main_grad(bias, lambda mg, acc: mg.add_(s) if acc else mg.copy_(s))
+                else:
+                    db = s.to(dout.dtype)
         return dx, db, dres, None, None
 
 
@@ -190,7 +200,7 @@ def bias_dropout_add(x, bias, residual, p=0.0, key=0):
 
 def _dropout_apply(x, p, key):
     x = x.contiguous()
-    if x.is_cuda:
+    if _lib.vec8_ok(8, x):   # flat: the kernel has a scalar tail, any numel
         y = torch.empty_like(x)
         _lib.kernels().dropout_fwd(_lib.dt_code(x.dtype), x.data_ptr(), y.data_ptr(),
                                    x.numel(), float(p), key, _lib.stream())

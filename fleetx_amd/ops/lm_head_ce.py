@@ -138,6 +138,8 @@ class _ChunkedHeadCE(torch.autograd.Function):
             else:
                 p = torch.exp(logits.float() - lse[:, None])
                 p[inr, local[inr]] -= 1.0
+                # ignored rows: exactly 0 whatever the mask holds (as ce_bwd does)
+                p[lc == ignore_index] = 0.0
                 logits = (p * gc[:, None]).to(logits.dtype)
             dh[r0:r1] = dgrad_gemm(logits, weight)
             # the tied weight's LM-head part: notified once, after the last chunk

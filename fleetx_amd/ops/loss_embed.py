@@ -27,30 +27,41 @@ def _allreduce(t, op, group):
     return t
 
 
+def ce_local_stats(x, lab, vocab_start, ignore_index):
+    """Per-row fp32 ``(max, sum-exp relative to that max, target logit)`` of
+    one vocab shard ``x`` [rows, V] whose first column is vocabulary entry
+    ``vocab_start``; the target is 0 where the label lies outside the shard
+    or is ignored.  Shards combine as ``M = max(m_i)``,
+    ``S = sum(s_i * exp(m_i - M))``, ``T = sum(t_i)``, ``loss = log S + M - T``."""
+    rows, V = x.shape
+    if x.is_cuda:
+        k = _lib.kernels()
+        mx = torch.empty(rows, device=x.device, dtype=torch.float32)
+        sm = torch.empty_like(mx)
+        tg = torch.empty_like(mx)
+        k.ce_stats(_lib.dt_code(x.dtype), x.data_ptr(), lab.data_ptr(), rows, V,
+                   int(vocab_start), mx.data_ptr(), sm.data_ptr(), tg.data_ptr(),
+                   int(ignore_index), _lib.stream())
+    else:
+        xf = x.float()
+        mx = xf.max(-1).values
+        sm = torch.exp(xf - mx[:, None]).sum(-1)
+        local = lab - vocab_start
+        inr = (local >= 0) & (local < V) & (lab != ignore_index)
+        tg = torch.where(inr, xf.gather(1, local.clamp(0, V - 1)[:, None])[:, 0],
+                         torch.zeros_like(mx))
+    return mx, sm, tg
+
+
 class _SoftmaxCE(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels, group, vocab_start, ignore_index, inplace_backward):
         V = logits.shape[-1]
         x = logits.reshape(-1, V)
         lab = labels.reshape(-1).contiguous()
-        rows = x.shape[0]
         if x.is_cuda:
             x = x.contiguous()
-            k = _lib.kernels()
-            mx = torch.empty(rows, device=x.device, dtype=torch.float32)
-            sm = torch.empty_like(mx)
-            tg = torch.empty_like(mx)
-            k.ce_stats(_lib.dt_code(x.dtype), x.data_ptr(), lab.data_ptr(), rows, V,
-                       int(vocab_start), mx.data_ptr(), sm.data_ptr(), tg.data_ptr(),
-                       int(ignore_index), _lib.stream())
-        else:
-            xf = x.float()
-            mx = xf.max(-1).values
-            sm = torch.exp(xf - mx[:, None]).sum(-1)
-            local = lab - vocab_start
-            inr = (local >= 0) & (local < V) & (lab != ignore_index)
-            tg = torch.where(inr, xf.gather(1, local.clamp(0, V - 1)[:, None])[:, 0],
-                             torch.zeros_like(mx))
+        mx, sm, tg = ce_local_stats(x, lab, vocab_start, ignore_index)
         if group is not None and group.nranks > 1:
             gmx = _allreduce(mx.clone(), dist.ReduceOp.MAX, group)
             pair = torch.stack([sm * torch.exp(mx - gmx), tg])
@@ -81,6 +92,7 @@ class _SoftmaxCE(torch.autograd.Function):
             onehot = torch.zeros_like(p)
             onehot[inr, local[inr]] = 1.0
             dx = ((p - onehot) * g[:, None]).to(x.dtype)
+            dx[lab == ctx.ignore_index] = 0   # exactly 0 whatever g holds (as ce_bwd does)
         return dx.view(ctx.shape), None, None, None, None, None
 
 
@@ -133,7 +145,9 @@ class _Embedding(torch.autograd.Function):
         vsize = weight.shape[0]
         ids_c = ids.reshape(-1).contiguous()
         pos_c = pos_ids.reshape(-1).contiguous() if pos_ids is not None else None
-        if weight.is_cuda:
+        # the forward kernel moves 16-byte vectors; the backward kernels are
+        # scalar per column and take any width
+        if _lib.vec8_ok(h, weight, pos_weight):
             out = torch.empty(ntok, h, device=weight.device, dtype=weight.dtype)
             _lib.kernels().embedding_fwd(_lib.dt_code(weight.dtype), ids_c.data_ptr(),
                                          _lib.ptr(pos_c), weight.data_ptr(), _lib.ptr(pos_weight),
@@ -144,7 +158,7 @@ class _Embedding(torch.autograd.Function):
             inr = (local >= 0) & (local < vsize)
             out = weight[local.clamp(0, vsize - 1)] * inr[:, None].to(weight.dtype)
             if pos_weight is not None:
-                out = out + pos_weight[pos_c]
+                out = (out.float() + pos_weight[pos_c].float()).to(weight.dtype)
         ctx.vocab_start, ctx.vsize, ctx.h = vocab_start, vsize, h
         ctx.has_pos = pos_weight is not None
         ctx.pos_rows = pos_weight.shape[0] if pos_weight is not None else 0

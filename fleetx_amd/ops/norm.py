@@ -61,6 +61,16 @@ def _into_main_grad(p, fill):
     grad_part_done(p)
 
 
+def _emit_grad(p, g32, dtype):
+    """A parameter gradient computed by a PyTorch formula branch: into the
+    fp32 ``main_grad`` when the parameter takes fused gradients on the GPU
+    (returns None), else returned in ``dtype``."""
+    if g32.is_cuda and _fused_param(p):
+        _into_main_grad(p, lambda mg, acc: mg.add_(g32) if acc else mg.copy_(g32))
+        return None
+    return g32.to(dtype)
+
+
 def _col_reduce_ln_main_grad(dy, s, mean, rstd, cols, dtype, weight, lnbias):
     """LN weight/bias gradients reduced over rows straight into the fp32
     ``main_grad`` of both parameters (no 16-bit grad, no autograd copy)."""
@@ -84,7 +94,7 @@ def _col_reduce_ln_main_grad(dy, s, mean, rstd, cols, dtype, weight, lnbias):
 
 def col_sum(x, cols):
     """Column sum of a [rows, cols] 16-bit tensor (fp32 accumulation)."""
-    if not x.is_cuda:
+    if not _lib.vec8_ok(cols, x):
         return x.reshape(-1, cols).float().sum(0).to(x.dtype)
     k = _lib.kernels()
     rows = x.numel() // cols
@@ -102,7 +112,8 @@ def col_sum_f32(x, dst, accumulate=False):
     """``dst (+)= x.reshape(-1, cols).sum(0)`` with ``dst`` a contiguous fp32
     vector (bias gradients straight into ``main_grad``)."""
     cols = dst.numel()
-    if not x.is_cuda:
+    x = x.contiguous()
+    if not _lib.vec8_ok(cols, x):
         s = x.reshape(-1, cols).float().sum(0).view_as(dst)
         if accumulate:
             dst.add_(s)
@@ -111,7 +122,6 @@ def col_sum_f32(x, dst, accumulate=False):
         return dst
     if dst.dtype != torch.float32 or not dst.is_contiguous():
         raise ValueError("col_sum_f32: dst must be contiguous fp32")
-    x = x.contiguous()
     k = _lib.kernels()
     rows = x.numel() // cols
     splits = k.coltile_splits(rows, cols)
@@ -188,9 +198,9 @@ class _AddLayerNorm(torch.autograd.Function):
         rows = x.numel() // h
         ctx.p, ctx.key, ctx.has_bias, ctx.has_res = p, key, bias is not None, residual is not None
         ctx.h = h
-        if x.is_cuda:
+        x = x.contiguous()
+        if _lib.vec8_ok(h, x, bias, residual, weight, lnbias):
             k = _lib.kernels()
-            x = x.contiguous()
             fused = bias is not None or residual is not None or p > 0
             # store_sum with nothing to add: s IS x (returned as an alias, no copy)
             s = torch.empty_like(x) if fused else None
@@ -205,10 +215,14 @@ class _AddLayerNorm(torch.autograd.Function):
             if s is None and store_sum:
                 s = x
         else:
-            v = x if bias is None else x + bias
-            v = _dropout_ref(v, p, key)
-            if residual is not None:
-                v = v + residual
+            v = x
+            if bias is not None or residual is not None or p > 0:
+                # fp32 like the kernel: s is rounded once, at the store
+                v = x.float() if bias is None else x.float() + bias.float()
+                v = _dropout_ref(v, p, key)
+                if residual is not None:
+                    v = v + residual.float()
+                v = v.to(x.dtype)
             s_saved = v
             s = v if (store_sum or bias is not None or residual is not None or p > 0) else None
             vf = v.float()
@@ -237,7 +251,7 @@ class _AddLayerNorm(torch.autograd.Function):
         dy = dy.contiguous()
         if ds_in is not None:
             ds_in = ds_in.contiguous()
-        if dy.is_cuda:
+        if _lib.vec8_ok(h, dy, ds_in, s, weight):
             k = _lib.kernels()
             dc = _lib.dt_code(dy.dtype)
             ds = torch.empty_like(dy)
@@ -272,9 +286,11 @@ class _AddLayerNorm(torch.autograd.Function):
                 dsf = dsf + ds_in.float().reshape(rows, h)
             ds = dsf.to(dy.dtype).reshape(dy.shape)
             dx = _dropout_ref(ds, ctx.p, ctx.key)
-            dw = (dy.float().reshape(rows, h) * xh).sum(0).to(weight.dtype)
-            db = dy.float().reshape(rows, h).sum(0).to(weight.dtype)
-            dbias = dx.float().reshape(rows, h).sum(0).to(dy.dtype) if ctx.has_bias else None
+            dw = _emit_grad(weight, (dy.float().reshape(rows, h) * xh).sum(0), weight.dtype)
+            db = _emit_grad(ctx.lnbias, dy.float().reshape(rows, h).sum(0), weight.dtype)
+            dbias = None
+            if ctx.has_bias:
+                dbias = _emit_grad(ctx.bias, dx.float().reshape(rows, h).sum(0), dy.dtype)
         dres = ds if ctx.has_res else None
         return dx, dbias, dres, dw, db, None, None, None, None
 
