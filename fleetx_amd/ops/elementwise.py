@@ -10,7 +10,8 @@ import math
 import torch
 
 from . import _lib
-from .norm import _dropout_ref, col_sum
+from .norm import _dropout_ref, col_sum, colsum_tickets
+from ..parallel import grad_sink as sink
 
 
 def _gelu_ref(x, erf):
@@ -62,7 +63,6 @@ class _BiasGelu(torch.autograd.Function):
             fin = {}
             if ctx.has_bias:
                 db = torch.empty(cols, device=x.device, dtype=bias.dtype)
-                from .norm import colsum_tickets
                 fin = {"cnt": colsum_tickets(x.device, cols), "out_t": db.data_ptr()}
             k.bias_gelu_bwd(dc, int(ctx.erf), dy.data_ptr(), x.data_ptr(), _lib.ptr(bias),
                             dx.data_ptr(), part.data_ptr(), rows, cols, splits, st, **fin)
@@ -105,7 +105,6 @@ def gelu_grad(dy, h, erf=False, colsum=None):
         fin = {}
         if colsum is not None:
             dst, acc = colsum
-            from .norm import colsum_tickets
             fin = {"cnt": colsum_tickets(h.device, cols), "out_f32": dst.data_ptr(),
                    "acc": int(acc)}
         k.bias_gelu_bwd(dc, int(erf), dy.data_ptr(), h.data_ptr(), 0,
@@ -114,8 +113,7 @@ def gelu_grad(dy, h, erf=False, colsum=None):
     dx = (dy.float() * _gelu_grad_ref(h.float(), erf)).to(h.dtype)
     if colsum is not None:
         dst, acc = colsum
-        s = dx.float().reshape(-1, dst.numel()).sum(0).view_as(dst)
-        dst.add_(s) if acc else dst.copy_(s)
+        sink.store_or_add(dst, dx.float().reshape(-1, dst.numel()).sum(0).view_as(dst), acc)
     return dx
 
 
@@ -152,8 +150,7 @@ class _BiasDropoutAdd(torch.autograd.Function):
         rows = dout.numel() // cols
         dres = dout if ctx.has_res else None
         bias = ctx.bias
-        fused = dout.is_cuda and bias is not None and getattr(bias, "_fx_fused_wgrad", False) \
-            and hasattr(bias, "main_grad")
+        fused = sink.fused(bias, on_gpu=dout)
         if _lib.vec8_ok(cols, dout):
             k = _lib.kernels()
             dc = _lib.dt_code(dout.dtype)
@@ -163,10 +160,9 @@ class _BiasDropoutAdd(torch.autograd.Function):
             if ctx.has_bias:
                 splits = k.coltile_splits(rows, cols)
                 part = torch.empty(splits, cols, device=dout.device, dtype=torch.float32)
-                from .norm import colsum_tickets
                 if fused:  # fp32 bias gradient straight into main_grad
-                    fin = {"out_f32": bias.main_grad.data_ptr(),
-                           "acc": int(not getattr(bias, "_fx_fresh", False))}
+                    mg, acc = sink.open_write(bias)
+                    fin = {"out_f32": mg.data_ptr(), "acc": int(acc)}
                 else:
                     db = torch.empty(cols, device=dout.device, dtype=dout.dtype)
                     fin = {"out_t": db.data_ptr()}
@@ -174,9 +170,7 @@ class _BiasDropoutAdd(torch.autograd.Function):
                                      part.data_ptr(), rows, cols, splits, float(ctx.p), ctx.key, st,
                                      cnt=colsum_tickets(dout.device, cols), **fin)
                 if fused:
-                    from ..parallel.linear import grad_part_done
-                    bias._fx_fresh = False
-                    grad_part_done(bias)
+                    sink.close_write(bias)
             elif ctx.p > 0:
                 k.dropout_fwd(dc, dout.data_ptr(), dx.data_ptr(), dout.numel(), float(ctx.p),
                               ctx.key, st)
@@ -184,12 +178,8 @@ class _BiasDropoutAdd(torch.autograd.Function):
             dx = _dropout_ref(dout, ctx.p, ctx.key)
             db = None
             if ctx.has_bias:
-                s = dx.float().reshape(rows, cols).sum(0)
-                if fused:
-                    from .norm import _into_main_grad
-                    _into_main_grad(bias, lambda mg, acc: mg.add_(s) if acc else mg.copy_(s))
-                else:
-                    db = s.to(dout.dtype)
+                db = sink.deliver(bias, dx.float().reshape(rows, cols).sum(0), dout.dtype,
+                                  on_gpu=True)
         return dx, db, dres, None, None
 
 
@@ -248,11 +238,7 @@ def transpose2d(x, out=None, colsum=None):
         out.copy_(x.t())
         if colsum is not None:
             dst, acc = colsum
-            s = x.float().sum(0)
-            if acc:
-                dst.add_(s.view_as(dst))
-            else:
-                dst.copy_(s.view_as(dst))
+            sink.store_or_add(dst, x.float().sum(0).view_as(dst), acc)
         return out
     k = _lib.kernels()
     part = None

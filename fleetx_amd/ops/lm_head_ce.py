@@ -37,6 +37,7 @@ import os
 import torch
 
 from . import _lib
+from ..parallel import grad_sink as sink
 
 _STATE = {"scale": None, "bad": None}
 
@@ -161,8 +162,7 @@ class _ChunkedHeadCE(torch.autograd.Function):
 def supported(h2, weight):
     """The fused path needs the tied weight's fp32 ``main_grad`` (the flat
     gradient buffer); on the CPU the CE statistics / gradient run in PyTorch."""
-    return (h2.dim() == 2 and getattr(weight, "_fx_fused_wgrad", False)
-            and hasattr(weight, "main_grad")
+    return (h2.dim() == 2 and sink.fused(weight)
             and (not h2.is_cuda or h2.dtype in (torch.bfloat16, torch.float16)))
 
 

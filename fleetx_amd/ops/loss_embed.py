@@ -14,6 +14,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
+from ..parallel import grad_sink as sink
 
 
 def _allreduce(t, op, group):
@@ -117,24 +118,21 @@ def _embedding_bwd(k, dc, ids, d, dw32, ntok, h, vstart, vsize, st):
     k.embedding_bwd(dc, ids.data_ptr(), d.data_ptr(), dw32.data_ptr(), ntok, h, vstart, vsize, st)
 
 
-def _grad_target(p, shape, device):
-    """fp32 buffer the scatter-add kernel accumulates into: the parameter's
-    flat-buffer ``main_grad`` when it takes fused gradients (no bf16 round
-    trip, no extra 4 B/elt copy), else a fresh zeroed tensor."""
-    if p is not None and getattr(p, "_fx_fused_wgrad", False) and hasattr(p, "main_grad"):
-        if getattr(p, "_fx_fresh", False):
-            p.main_grad.zero_()
-            p._fx_fresh = False
-        return p.main_grad, True
-    return torch.zeros(*shape, device=device, dtype=torch.float32), False
-
-
-def _grad_finish(p, g32, fused, dtype):
-    if fused:
-        from ..parallel.linear import grad_part_done
-        grad_part_done(p)
-        return None
-    return g32.to(dtype)
+def _scatter_grad(p, shape, device, dtype, scatter_add):
+    """``scatter_add(fp32 buffer)`` accumulates a table's gradient: into the
+    parameter's flat-buffer ``main_grad`` when it takes fused gradients (no
+    bf16 round trip, no extra 4 B/elt copy; returns None), else into a fresh
+    zeroed tensor returned in ``dtype``."""
+    if not sink.fused(p):
+        g32 = torch.zeros(*shape, device=device, dtype=torch.float32)
+        scatter_add(g32)
+        return g32.to(dtype)
+    mg, accumulate = sink.open_write(p)
+    if not accumulate:  # the scatter-add kernels have no beta = 0 mode
+        mg.zero_()
+    scatter_add(mg)
+    sink.close_write(p)
+    return None
 
 
 class _Embedding(torch.autograd.Function):
@@ -178,25 +176,26 @@ class _Embedding(torch.autograd.Function):
             k = _lib.kernels()
             dc = _lib.dt_code(d.dtype)
             st = _lib.stream()
-            wp, pp = ctx.params
-            dw32, fused = _grad_target(wp, (ctx.vsize, h), d.device)
-            _embedding_bwd(k, dc, ids_c, d, dw32, ntok, h, int(ctx.vocab_start), ctx.vsize, st)
-            dw = _grad_finish(wp, dw32, fused, ctx.wdtype)
-            if ctx.has_pos:
-                dp32, fused = _grad_target(pp, (ctx.pos_rows, h), d.device)
-                _embedding_bwd(k, dc, pos_c, d, dp32, ntok, h, 0, ctx.pos_rows, st)
-                dpos = _grad_finish(pp, dp32, fused, ctx.wdtype)
+            vstart = int(ctx.vocab_start)
+
+            def word(g32):
+                _embedding_bwd(k, dc, ids_c, d, g32, ntok, h, vstart, ctx.vsize, st)
+
+            def pos(g32):
+                _embedding_bwd(k, dc, pos_c, d, g32, ntok, h, 0, ctx.pos_rows, st)
         else:
-            wp, pp = ctx.params
             local = ids_c - ctx.vocab_start
             inr = (local >= 0) & (local < ctx.vsize)
-            dw32, fused = _grad_target(wp, (ctx.vsize, h), d.device)
-            dw32.index_add_(0, local[inr], d[inr].float())
-            dw = _grad_finish(wp, dw32, fused, ctx.wdtype)
-            if ctx.has_pos:
-                dp32, fused = _grad_target(pp, (ctx.pos_rows, h), d.device)
-                dp32.index_add_(0, pos_c, d.float())
-                dpos = _grad_finish(pp, dp32, fused, ctx.wdtype)
+
+            def word(g32):
+                g32.index_add_(0, local[inr], d[inr].float())
+
+            def pos(g32):
+                g32.index_add_(0, pos_c, d.float())
+        wp, pp = ctx.params
+        dw = _scatter_grad(wp, (ctx.vsize, h), d.device, ctx.wdtype, word)
+        if ctx.has_pos:
+            dpos = _scatter_grad(pp, (ctx.pos_rows, h), d.device, ctx.wdtype, pos)
         return None, dw, None, dpos, None
 
 

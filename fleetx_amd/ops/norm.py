@@ -11,7 +11,7 @@ import os
 import torch
 
 from . import _lib
-from ..parallel import rng as _rng
+from ..parallel import grad_sink as sink, rng as _rng
 
 
 _TICKETS = {}
@@ -32,79 +32,48 @@ def colsum_tickets(device, cols):
     return t.data_ptr()
 
 
-def _col_reduce_ln(dy, s, mean, rstd, cols, dtype):
+_TARGET_KW = (("f0", "t0", "acc0"), ("f1", "t1", "acc1"))
+
+
+def _coltile(mode, x, aux, rows, cols, targets):
+    """One column-tile reduction over the rows of ``x`` [rows, cols]: mode 1
+    sums the columns (one target), mode 0 reduces the LayerNorm weight and
+    bias gradients of ``dy = x`` with ``aux = (s, mean, rstd)`` pointers (two
+    targets).  ``targets``: ``(f32_ptr, t16_ptr, accumulate)`` per result --
+    added into / stored to fp32, or stored in the 16-bit type of ``x``."""
     k = _lib.kernels()
-    rows = dy.numel() // cols
     splits = k.coltile_splits(rows, cols)
-    p0 = torch.empty(splits, cols, device=dy.device, dtype=torch.float32)
-    p1 = torch.empty_like(p0)
-    st = _lib.stream()
-    dc = _lib.dt_code(dtype)
-    dg = torch.empty(cols, device=dy.device, dtype=dtype)
-    db = torch.empty(cols, device=dy.device, dtype=dtype)
-    k.coltile_partial(dc, 0, dy.data_ptr(), s.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                      p0.data_ptr(), p1.data_ptr(), rows, cols, splits, st,
-                      cnt=colsum_tickets(dy.device, cols), t0=dg.data_ptr(), t1=db.data_ptr())
-    return dg, db
+    p0 = torch.empty(splits, cols, device=x.device, dtype=torch.float32)
+    p1 = torch.empty_like(p0) if mode == 0 else None
+    fin = {}
+    for (kf, kt, ka), (f32, t16, acc) in zip(_TARGET_KW, targets):
+        if f32:
+            fin[kf], fin[ka] = f32, acc
+        else:
+            fin[kt] = t16
+    k.coltile_partial(_lib.dt_code(x.dtype), mode, x.data_ptr(), *aux, p0.data_ptr(),
+                      _lib.ptr(p1), rows, cols, splits, _lib.stream(),
+                      cnt=colsum_tickets(x.device, cols), **fin)
 
 
-def _fused_param(p):
-    return p is not None and getattr(p, "_fx_fused_wgrad", False) and hasattr(p, "main_grad")
-
-
-def _into_main_grad(p, fill):
-    """Write (first contribution of the step) or accumulate a parameter's
-    gradient straight into its fp32 ``main_grad`` and report it ready."""
-    from ..parallel.linear import grad_part_done
-    fill(p.main_grad, not getattr(p, "_fx_fresh", False))
-    p._fx_fresh = False
-    grad_part_done(p)
-
-
-def _emit_grad(p, g32, dtype):
-    """A parameter gradient computed by a PyTorch formula branch: into the
-    fp32 ``main_grad`` when the parameter takes fused gradients on the GPU
-    (returns None), else returned in ``dtype``."""
-    if g32.is_cuda and _fused_param(p):
-        _into_main_grad(p, lambda mg, acc: mg.add_(g32) if acc else mg.copy_(g32))
-        return None
-    return g32.to(dtype)
-
-
-def _col_reduce_ln_main_grad(dy, s, mean, rstd, cols, dtype, weight, lnbias):
-    """LN weight/bias gradients reduced over rows straight into the fp32
-    ``main_grad`` of both parameters (no 16-bit grad, no autograd copy)."""
-    k = _lib.kernels()
-    rows = dy.numel() // cols
-    splits = k.coltile_splits(rows, cols)
-    p0 = torch.empty(splits, cols, device=dy.device, dtype=torch.float32)
-    p1 = torch.empty_like(p0)
-    st = _lib.stream()
-    dc = _lib.dt_code(dtype)
-    acc = [int(not getattr(prm, "_fx_fresh", False)) for prm in (weight, lnbias)]
-    k.coltile_partial(dc, 0, dy.data_ptr(), s.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                      p0.data_ptr(), p1.data_ptr(), rows, cols, splits, st,
-                      cnt=colsum_tickets(dy.device, cols), f0=weight.main_grad.data_ptr(),
-                      acc0=acc[0], f1=lnbias.main_grad.data_ptr(), acc1=acc[1])
-    from ..parallel.linear import grad_part_done
-    for prm in (weight, lnbias):
-        prm._fx_fresh = False
-        grad_part_done(prm)
+def _col_target(prm, direct, cols, like):
+    """A column-reduction target for the gradient of ``prm``: the
+    ``(f32_ptr, t16_ptr, accumulate)`` triple and the tensor to hand to
+    autograd -- ``main_grad`` and None when the parameter takes ``direct``
+    writes, else a fresh 16-bit vector."""
+    if direct:
+        mg, acc = sink.open_write(prm)
+        return (mg.data_ptr(), 0, int(acc)), None
+    g = torch.empty(cols, device=like.device, dtype=like.dtype)
+    return (0, g.data_ptr(), 0), g
 
 
 def col_sum(x, cols):
     """Column sum of a [rows, cols] 16-bit tensor (fp32 accumulation)."""
     if not _lib.vec8_ok(cols, x):
         return x.reshape(-1, cols).float().sum(0).to(x.dtype)
-    k = _lib.kernels()
-    rows = x.numel() // cols
-    splits = k.coltile_splits(rows, cols)
-    p0 = torch.empty(splits, cols, device=x.device, dtype=torch.float32)
-    st = _lib.stream()
-    dc = _lib.dt_code(x.dtype)
     out = torch.empty(cols, device=x.device, dtype=x.dtype)
-    k.coltile_partial(dc, 1, x.data_ptr(), 0, 0, 0, p0.data_ptr(), 0, rows, cols, splits, st,
-                      cnt=colsum_tickets(x.device, cols), t0=out.data_ptr())
+    _coltile(1, x, (0, 0, 0), x.numel() // cols, cols, [(0, out.data_ptr(), 0)])
     return out
 
 
@@ -114,23 +83,11 @@ def col_sum_f32(x, dst, accumulate=False):
     cols = dst.numel()
     x = x.contiguous()
     if not _lib.vec8_ok(cols, x):
-        s = x.reshape(-1, cols).float().sum(0).view_as(dst)
-        if accumulate:
-            dst.add_(s)
-        else:
-            dst.copy_(s)
+        sink.store_or_add(dst, x.reshape(-1, cols).float().sum(0).view_as(dst), accumulate)
         return dst
     if dst.dtype != torch.float32 or not dst.is_contiguous():
         raise ValueError("col_sum_f32: dst must be contiguous fp32")
-    k = _lib.kernels()
-    rows = x.numel() // cols
-    splits = k.coltile_splits(rows, cols)
-    p0 = torch.empty(splits, cols, device=x.device, dtype=torch.float32)
-    st = _lib.stream()
-    dc = _lib.dt_code(x.dtype)
-    k.coltile_partial(dc, 1, x.data_ptr(), 0, 0, 0, p0.data_ptr(), 0, rows, cols, splits, st,
-                      cnt=colsum_tickets(x.device, cols), f0=dst.data_ptr(),
-                      acc0=int(accumulate))
+    _coltile(1, x, (0, 0, 0), x.numel() // cols, cols, [(dst.data_ptr(), 0, int(accumulate))])
     return dst
 
 
@@ -150,10 +107,6 @@ def _ln_bwd_cols_max_h():
     return {"0": 0, "2": 4096}.get(mode, 1536)
 
 
-def _main_grad_target(p):
-    return _fused_param(p) and p.main_grad.dtype == torch.float32 and p.main_grad.is_contiguous()
-
-
 def _ln_bwd_cols(k, dc, dy, s, mean, rstd, weight, ctx, ds_in, ds, dx, rows, h):
     """LayerNorm backward and its column sums (dgamma, dbeta and, with a fused
     residual + bias, the bias gradient ``sum(dx)``) in one row pass plus one
@@ -163,19 +116,13 @@ def _ln_bwd_cols(k, dc, dy, s, mean, rstd, weight, ctx, ds_in, ds, dx, rows, h):
     G = k.ln_bwd_cols_blocks(rows, h, 4096)
     with_db = bool(ctx.has_bias)
     part = torch.empty(3 if with_db else 2, G, h, device=dy.device, dtype=torch.float32)
-    outs, grads, done = [], [], []
-    for prm, want in ((weight, True), (ctx.lnbias, True), (ctx.bias, with_db)):
-        if not want:
-            outs.append((0, 0, 0))
-            grads.append(None)
-        elif _main_grad_target(prm):
-            outs.append((prm.main_grad.data_ptr(), 0, int(not getattr(prm, "_fx_fresh", False))))
-            grads.append(None)
-            done.append(prm)
-        else:
-            g = torch.empty(h, device=dy.device, dtype=dy.dtype)
-            outs.append((0, g.data_ptr(), 0))
-            grads.append(g)
+    prms = (weight, ctx.lnbias, ctx.bias if with_db else None)
+    outs, grads = [], []
+    for prm in prms:
+        t, g = ((0, 0, 0), None) if prm is None else \
+            _col_target(prm, sink.fused(prm, fp32_contiguous=True), h, dy)
+        outs.append(t)
+        grads.append(g)
     (fg, tg, ag), (fb, tb, ab), (fx, tx, ax) = outs
     rc = k.ln_bwd_cols(dc, dy.data_ptr(), s.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
                        weight.data_ptr(), _lib.ptr(ds_in), ds.data_ptr(), dx.data_ptr(), rows, h,
@@ -183,12 +130,10 @@ def _ln_bwd_cols(k, dc, dy, s, mean, rstd, weight, ctx, ds_in, ds, dx, rows, h):
                        ab, fx, tx, ax, _lib.stream())
     if rc != 0:
         raise RuntimeError("ln_bwd_cols: shape rows=%d h=%d not covered" % (rows, h))
-    if done:
-        from ..parallel.linear import grad_part_done
-        for prm in done:
-            prm._fx_fresh = False
-            grad_part_done(prm)
-    return grads[0], grads[1], grads[2]
+    for prm, (f32, _, _) in zip(prms, outs):
+        if f32:
+            sink.close_write(prm)
+    return grads
 
 
 class _AddLayerNorm(torch.autograd.Function):
@@ -264,15 +209,18 @@ class _AddLayerNorm(torch.autograd.Function):
             k.ln_bwd_row(dc, dy.data_ptr(), s.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
                          weight.data_ptr(), _lib.ptr(ds_in), ds.data_ptr(), dx.data_ptr(), rows, h,
                          float(ctx.p), ctx.key, _lib.stream())
-            if _fused_param(weight) and _fused_param(ctx.lnbias):
-                _col_reduce_ln_main_grad(dy, s, mean, rstd, h, dy.dtype, weight, ctx.lnbias)
-                dw = db = None
-            else:
-                dw, db = _col_reduce_ln(dy, s, mean, rstd, h, dy.dtype)
+            direct = sink.fused(weight) and sink.fused(ctx.lnbias)
+            (tw, dw), (tb, db) = (_col_target(prm, direct, h, dy) for prm in (weight, ctx.lnbias))
+            _coltile(0, dy, (s.data_ptr(), mean.data_ptr(), rstd.data_ptr()), rows, h, [tw, tb])
+            if direct:
+                sink.close_write(weight)
+                sink.close_write(ctx.lnbias)
             dbias = None
             if ctx.has_bias:
-                if _fused_param(ctx.bias):
-                    _into_main_grad(ctx.bias, lambda mg, acc: col_sum_f32(dx, mg, acc))
+                if sink.fused(ctx.bias):
+                    mg, acc = sink.open_write(ctx.bias)
+                    col_sum_f32(dx, mg, acc)
+                    sink.close_write(ctx.bias)
                 else:
                     dbias = col_sum(dx, h)
         else:
@@ -286,11 +234,14 @@ class _AddLayerNorm(torch.autograd.Function):
                 dsf = dsf + ds_in.float().reshape(rows, h)
             ds = dsf.to(dy.dtype).reshape(dy.shape)
             dx = _dropout_ref(ds, ctx.p, ctx.key)
-            dw = _emit_grad(weight, (dy.float().reshape(rows, h) * xh).sum(0), weight.dtype)
-            db = _emit_grad(ctx.lnbias, dy.float().reshape(rows, h).sum(0), weight.dtype)
+            dw = sink.deliver(weight, (dy.float().reshape(rows, h) * xh).sum(0), weight.dtype,
+                              on_gpu=True)
+            db = sink.deliver(ctx.lnbias, dy.float().reshape(rows, h).sum(0), weight.dtype,
+                              on_gpu=True)
             dbias = None
             if ctx.has_bias:
-                dbias = _emit_grad(ctx.bias, dx.float().reshape(rows, h).sum(0), dy.dtype)
+                dbias = sink.deliver(ctx.bias, dx.float().reshape(rows, h).sum(0), dy.dtype,
+                                     on_gpu=True)
         dres = ds if ctx.has_res else None
         return dx, dbias, dres, dw, db, None, None, None, None
 

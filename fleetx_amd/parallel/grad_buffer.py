@@ -37,7 +37,7 @@ import os
 import torch
 import torch.distributed as dist
 
-from .linear import grad_part_done
+from . import grad_sink as sink
 
 ALIGN = 128  # elements (256 B in bf16, 512 B in fp32)
 
@@ -262,19 +262,9 @@ class FlatParamGradBuffer:
 
     def _make_hook(self, p):
         def hook(param):
-            g = param.grad
-            if g is None:
-                # fires with no grad when a fused-wgrad Function already wrote
-                # main_grad and returned None: readiness was signalled there
-                return
-            if param._fx_fresh:
-                param.main_grad.copy_(g)
-            else:
-                param.main_grad.add_(g)
-            param._fx_fresh = False
-            param._fx_sq_ok = False  # this write left no norm partials
-            param.grad = None
-            grad_part_done(param)
+            if param.grad is not None:
+                param._fx_sq_ok = False  # this write leaves no norm partials
+            sink.absorb(param)
         return hook
 
     # ------------------------------------------------------------------ control

@@ -15,7 +15,10 @@ an extra read-modify-write of the whole fp32 gradient (~22 ms per step for
 GPT-3 6.7B on one MI355X, measured with rocprofv3) plus the bf16 temporaries.
 Here the wgrad GEMM writes fp32 directly (``mm``/``addmm`` with
 ``out_dtype=float32``, beta = 0 for the first micro-batch of a step and 1
-afterwards), so the flat gradient buffer is never zero-filled either.
+afterwards), so the flat gradient buffer is never zero-filled either.  Who may
+write ``main_grad``, overwrite or accumulate, and the report to the gradient
+buffer are the protocol of ``parallel.grad_sink``; every producer here opens
+and closes its writes through it.
 
 Operand layout: the reduction of the wgrad GEMM runs over tokens, the slow
 axis of both row-major activations, and hipBLASLt's kernels for that "NT"
@@ -29,6 +32,8 @@ import torch
 import torch.nn.functional as F
 
 from ..ops import gemm as G
+from . import grad_sink as sink
+from .grad_sink import grad_part_done  # noqa: F401  (re-export)
 
 _MM_DTYPE_OUT = None
 
@@ -61,10 +66,6 @@ def dgrad(dy, w):
         from ..ops.elementwise import transpose2d
         return F.linear(dy, transpose2d(w))
     return torch.matmul(dy, w)
-
-
-def _fused(p):
-    return p is not None and getattr(p, "_fx_fused_wgrad", False) and hasattr(p, "main_grad")
 
 
 def _tn_operands(dy2, x2, colsum=None):
@@ -122,7 +123,7 @@ def accumulate_wgrad(weight, dy2, x2, bias=None, notify=True):
     # flight on two streams can deadlock (workgroups of one spin on tiles the
     # other's resident workgroups keep from being scheduled; seen on ViT-g)
     side = None
-    if dy2.is_cuda and (bias is None or _fused(bias)) and \
+    if dy2.is_cuda and (bias is None or sink.fused(bias)) and \
             getattr(weight, "_fx_grad_parts", 1) == 1 and G.use("wgrad", dy2, x2) and \
             G.covers_wgrad(dy2, x2):
         side = _wgrad_side_stream(dy2.device)
@@ -153,8 +154,8 @@ def _accumulate_wgrad(weight, dy2, x2, bias=None, notify=True, bias_notify=True,
                       kernel_only=False):
     """``kernel_only``: return ``_DECLINED`` (nothing written) instead of
     running the hipBLASLt fallback when the MFMA kernel declines."""
-    mg = weight.main_grad
-    fresh = getattr(weight, "_fx_fresh", False)
+    mg, acc = sink.open_write(weight)
+    fresh = not acc
     # gradient-norm partials from the epilogue (grad_buffer.enable_fused_norm):
     # valid only while EVERY write of this step's gradient produced them
     sq = getattr(weight, "_fx_sq", None)
@@ -171,43 +172,37 @@ def _accumulate_wgrad(weight, dy2, x2, bias=None, notify=True, bias_notify=True,
         weight._fx_sq_ok = False
     if not done and kernel_only:
         return _DECLINED
-    if done:
-        db = None
-        if bias is not None:
-            if _fused(bias):
-                colsum_into(dy2, bias.main_grad, not getattr(bias, "_fx_fresh", False))
-                bias._fx_fresh = False
-                if bias_notify:
-                    grad_part_done(bias)
-            else:
-                db = torch.empty(bias.shape, device=dy2.device, dtype=torch.float32)
-                colsum_into(dy2, db, False)
-                db = db.to(bias.dtype)
-        weight._fx_fresh = False
-        if notify:
-            grad_part_done(weight)
-        return db
     db, colsum = None, None
     if bias is not None:
-        if _fused(bias):
-            colsum = (bias.main_grad, not getattr(bias, "_fx_fresh", False))
-        else:
-            db = torch.empty(bias.shape, device=dy2.device, dtype=torch.float32)
-            colsum = (db, False)
-    tn = _tn_operands(dy2, x2, colsum)
-    if tn is None and colsum is not None:
-        s = dy2.float().sum(0)
-        if colsum[1]:
-            colsum[0].add_(s)
-        else:
-            colsum[0].copy_(s)
+        direct = sink.fused(bias)
+        colsum = sink.open_write(bias) if direct else _scratch_f32(bias, dy2.device)
+    if done:
+        tn = None
+        if colsum is not None:
+            colsum_into(dy2, *colsum)
+    else:
+        tn = _tn_operands(dy2, x2, colsum)
+        if tn is None and colsum is not None:
+            sink.store_or_add(colsum[0], dy2.float().sum(0), colsum[1])
     if bias is not None:
-        if db is None:
-            bias._fx_fresh = False
-            if bias_notify:
-                grad_part_done(bias)
+        if direct:
+            sink.close_write(bias, bias_notify)
         else:
-            db = db.to(bias.dtype)
+            db = colsum[0].to(bias.dtype)
+    if not done:
+        _vendor_wgrad(mg, fresh, dy2, x2, tn)
+    sink.close_write(weight, notify)
+    return db
+
+
+def _scratch_f32(bias, device):
+    """``(fp32 target, accumulate)`` for the column sums of a bias gradient
+    that goes back to autograd, in the form ``sink.open_write`` returns."""
+    return torch.empty(bias.shape, device=device, dtype=torch.float32), False
+
+
+def _vendor_wgrad(mg, fresh, dy2, x2, tn):
+    """``mg (+)= dy2^T @ x2`` on hipBLASLt (``tn``: the transposed operands)."""
     a, b = tn if tn is not None else (dy2.t(), x2)
     if mg.dtype != torch.float32:
         # 16-bit gradient storage (grad_dtype): the vendor GEMM's own fp32
@@ -232,25 +227,6 @@ def _accumulate_wgrad(weight, dy2, x2, bias=None, notify=True, bias_notify=True,
             mg.copy_(g)
         else:
             mg.add_(g)
-    weight._fx_fresh = False
-    if notify:
-        grad_part_done(weight)
-    return db
-
-
-def grad_part_done(p):
-    """One fused contribution to ``p.main_grad`` is in.  A weight used twice in
-    a step (the tied word embedding: lookup + LM head, ``_fx_grad_parts = 2``)
-    is reported ready to the gradient buffer only after its last part."""
-    parts = getattr(p, "_fx_grad_parts", 1)
-    if parts > 1:
-        p._fx_parts_seen = getattr(p, "_fx_parts_seen", 0) + 1
-        if p._fx_parts_seen < parts:
-            return
-        p._fx_parts_seen = 0
-    cb = getattr(p, "_fx_grad_ready", None)
-    if cb is not None:
-        cb()
 
 
 def fwd_gemm(x, weight, bias=None):
@@ -322,8 +298,7 @@ class _FusedWgradLinear(torch.autograd.Function):
 def linear(x, weight, bias=None):
     """``F.linear`` whose weight gradient lands in ``weight.main_grad`` when the
     weight lives in a :class:`FlatParamGradBuffer` (training); plain otherwise."""
-    if torch.is_grad_enabled() and weight.requires_grad and hasattr(weight, "main_grad") \
-            and getattr(weight, "_fx_fused_wgrad", False):
+    if torch.is_grad_enabled() and weight.requires_grad and sink.fused(weight):
         return _FusedWgradLinear.apply(x, weight, bias)
     return F.linear(x, weight, bias)
 
@@ -334,7 +309,7 @@ def linear(x, weight, bias=None):
 def _wgrad(w, dy2, x2):
     """fp32 fused accumulation when the weight lives in a flat grad buffer,
     else a plain dW to hand back to autograd."""
-    if hasattr(w, "main_grad") and getattr(w, "_fx_fused_wgrad", False):
+    if sink.fused(w):
         accumulate_wgrad(w, dy2, x2)
         return None
     if G.use("wgrad", dy2, x2):
@@ -453,18 +428,14 @@ class _FusedMLP(torch.autograd.Function):
         dw2 = _wgrad(w2, dy2, a)
         # db1 = colsum(dH) from the same pass as dH where possible; fp32 straight
         # into main_grad when the bias lives in the flat buffer
-        db1, cs, into_main = None, None, False
+        db1, cs = None, None
         if b1 is not None:
-            if hasattr(b1, "main_grad") and getattr(b1, "_fx_grad_ready", None) is not None:
-                cs = (b1.main_grad, not getattr(b1, "_fx_fresh", False))
-                into_main = True
-            else:
-                cs = (torch.empty(b1.shape, device=dy.device, dtype=torch.float32), False)
+            direct = sink.in_buffer(b1)
+            cs = sink.open_write(b1) if direct else _scratch_f32(b1, dy.device)
         dh = dgrad_gemm(dy2, w2, act_input=h, act=ctx.act, colsum=cs)
         if b1 is not None:
-            if into_main:
-                b1._fx_fresh = False
-                grad_part_done(b1)
+            if direct:
+                sink.close_write(b1)
             else:
                 db1 = cs[0].to(b1.dtype)
         dw1 = _wgrad(w1, dh, x2)

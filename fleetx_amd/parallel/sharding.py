@@ -52,7 +52,7 @@ import contextlib
 import torch
 import torch.distributed as dist
 
-from .linear import grad_part_done
+from . import grad_sink as sink
 from .grad_buffer import ALIGN, Category, _is_gloo, _round_up, default_decay_fn
 
 
@@ -345,16 +345,7 @@ class Stage3ParamGradBuffer:
             self._gather(self.units[u.idx - 1])
 
     def _accum_hook(self, param):
-        g = param.grad
-        if g is None:  # fused-wgrad Functions already wrote main_grad
-            return
-        if param._fx_fresh:
-            param.main_grad.copy_(g)
-        else:
-            param.main_grad.add_(g)
-        param._fx_fresh = False
-        param.grad = None
-        grad_part_done(param)
+        sink.absorb(param)
 
     def _make_ready(self, p):
         def ready():

@@ -40,7 +40,9 @@ sequence order, so QKV and the output projection keep it.
 import torch
 import torch.distributed as dist
 
-from .linear import accumulate_wgrad, grad_part_done, G
+from . import grad_sink as sink
+from .grad_sink import grad_part_done
+from .linear import accumulate_wgrad, G
 
 SP_CHUNKS = {"chunks": 2}
 
@@ -81,13 +83,11 @@ def _wgrad_chunks(weight, pairs, want_bias):
     """Weight (and bias) gradient from (dy2, x2) row blocks.  Fused fp32
     main_grad accumulation when the weight lives in a flat grad buffer (the
     buffer is notified once, after the last block); else a plain tensor."""
-    fused = hasattr(weight, "main_grad") and getattr(weight, "_fx_fused_wgrad", False)
-    if fused:
+    dw = None
+    if sink.fused(weight):
         for i, (dy2, x2) in enumerate(pairs):
             accumulate_wgrad(weight, dy2, x2, notify=(i == len(pairs) - 1))
-        dw = None
     else:
-        dw = None
         for dy2, x2 in pairs:
             part = torch.mm(dy2.t(), x2)
             dw = part if dw is None else dw.add_(part)

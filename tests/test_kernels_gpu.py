@@ -721,6 +721,108 @@ def test_tn_wgrad_matches_direct():
         torch.testing.assert_close(db.float(), dy.float().sum(0), rtol=1e-2, atol=1e-1)
 
 
+# ---------------------------------------------------------------- gradient sink
+# Every producer's kernel branch, once with plain parameters (16-bit gradient
+# through autograd) and once with parameters that take direct fp32 writes into
+# main_grad.  272 rows: past one 256-row transpose / TN block and no multiple
+# of the 16-row column tile times its splits; width 264: a multiple of 8, two
+# 128-column tiles and a ragged third; LayerNorm also at 2056, above the
+# one-pass backward's 1536 (row kernel + column-tile passes).
+_SR, _SW = 272, 264
+
+
+def _sink_linear(w, dt, mk):
+    from fleetx_amd.parallel.linear import linear
+    x = torch.randn(_SR, 256, device=DEV).to(dt)
+    prm = {"weight": mk(0.05 * torch.randn(w, 256, device=DEV)), "bias": mk(torch.randn(w, device=DEV))}
+    return prm, lambda: linear(x, prm["weight"], prm["bias"])
+
+
+def _sink_fused_mlp(w, dt, mk):
+    from fleetx_amd.parallel.linear import fused_mlp
+    x = torch.randn(_SR, w, device=DEV).to(dt).requires_grad_()
+    # FC1's bias: in the buffer without having opted into fused gradients
+    prm = {"w1": mk(0.05 * torch.randn(w, w, device=DEV)),
+           "b1": mk(torch.randn(w, device=DEV), fused=False),
+           "w2": mk(0.05 * torch.randn(w, w, device=DEV))}
+    return prm, lambda: fused_mlp(x, prm["w1"], prm["b1"], prm["w2"])
+
+
+def _sink_add_layer_norm(w, dt, mk):
+    from fleetx_amd import ops
+    x = torch.randn(_SR, w, device=DEV).to(dt)
+    res = torch.randn(_SR, w, device=DEV).to(dt)
+    prm = {"bias": mk(torch.randn(w, device=DEV)), "ln_w": mk(1 + 0.1 * torch.randn(w, device=DEV)),
+           "ln_b": mk(0.1 * torch.randn(w, device=DEV))}
+
+    def fwd():
+        s, y = ops.add_layer_norm(x, prm["bias"], res, prm["ln_w"], prm["ln_b"], 1e-5, 0.1, 4321)
+        return s * 0.5 + y
+    return prm, fwd
+
+
+def _sink_bias_dropout_add(w, dt, mk):
+    from fleetx_amd import ops
+    x = torch.randn(_SR, w, device=DEV).to(dt)
+    res = torch.randn(_SR, w, device=DEV).to(dt)
+    prm = {"bias": mk(torch.randn(w, device=DEV))}
+    return prm, lambda: ops.bias_dropout_add(x, prm["bias"], res, 0.1, 4321)
+
+
+def _sink_embedding(w, dt, mk):
+    from fleetx_amd.ops.loss_embed import embedding
+    ids = torch.randint(0, 300, (_SR,), device=DEV)
+    pos = torch.arange(_SR, device=DEV)
+    prm = {"word": mk(torch.randn(300, w, device=DEV)), "pos": mk(torch.randn(_SR, w, device=DEV))}
+    return prm, lambda: embedding(ids, prm["word"], pos, prm["pos"])
+
+
+def _sink_backward(fwd):
+    # upstream gradient in eighths: the embedding's atomic scatter-add, which
+    # always accumulates onto main_grad, then sums exactly in any order
+    y = fwd()
+    torch.manual_seed(1)
+    y.backward((torch.randint(-8, 9, y.shape, device=DEV) / 8).to(y.dtype))
+
+
+_SINK_CASES = [(_sink_linear, _SW), (_sink_fused_mlp, _SW), (_sink_add_layer_norm, _SW),
+               (_sink_add_layer_norm, 2056), (_sink_bias_dropout_add, _SW), (_sink_embedding, _SW)]
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
+@pytest.mark.parametrize("producer,width", _SINK_CASES,
+                         ids=["%s-%d" % (f.__name__[6:], w) for f, w in _SINK_CASES])
+def test_fused_gradients_match_plain_through_the_kernels(producer, width, dt):
+    def plain(t, fused=True):
+        return torch.nn.Parameter(t.to(dt))
+
+    def sinked(t, fused=True):
+        p = plain(t)
+        p.main_grad = torch.full(t.shape, 7.0, device=DEV)
+        p._fx_fresh, p._fx_fused_wgrad = True, fused
+        p.fired = []
+        p._fx_grad_ready = lambda: p.fired.append(1)
+        return p
+
+    torch.manual_seed(0)
+    ref, fwd = producer(width, dt, plain)
+    _sink_backward(fwd)
+    torch.manual_seed(0)
+    prm, fwd = producer(width, dt, sinked)
+    _sink_backward(fwd)
+    once = {}
+    for name, p in prm.items():
+        assert p.grad is None, name                      # nothing was left to autograd
+        # both are roundings of one fp32 value (bitwise on the previous tree too)
+        assert torch.equal(p.main_grad.to(dt), ref[name].grad), name
+        assert p.fired == [1] and not p._fx_fresh, name
+        once[name] = p.main_grad.clone()
+    _sink_backward(fwd)                                  # no zero_grad: accumulates
+    for name, p in prm.items():
+        assert torch.equal(p.main_grad, 2 * once[name]), name
+        assert p.fired == [1, 1], name
+
+
 # ---------------------------------------------------------------- fused sampling (K18)
 @pytest.mark.parametrize("T,k,p", [(1.0, 50, 1.0), (0.7, 0, 0.9), (0.8, 40, 0.8), (1.3, 0, 1.0)])
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
