@@ -12,115 +12,7 @@
 namespace py = pybind11;
 typedef uintptr_t ptr;
 
-extern "C" {
-int fx_coltile_splits(int rows, int cols);
-void fx_add_ln_fwd(int, const void*, const void*, const void*, const void*, const void*, void*,
-                   void*, float*, float*, int, int, float, float, uint64_t, hipStream_t);
-void fx_ln_bwd_row(int, const void*, const void*, const float*, const float*, const void*,
-                   const void*, void*, void*, int, int, float, uint64_t, hipStream_t);
-int fx_ln_bwd_cols_blocks(int, int, int);
-int fx_ln_bwd_cols(int, const void*, const void*, const float*, const float*, const void*,
-                   const void*, void*, void*, int, int, float, uint64_t, float*, int, float*, void*,
-                   int, float*, void*, int, float*, void*, int, hipStream_t);
-void fx_coltile_partial(int, int, const void*, const void*, const float*, const float*, float*,
-                        float*, int, int, int, hipStream_t, int*, float*, void*, int, float*,
-                        void*, int);
-void fx_coltile_finalize(int, const float*, int, int, float*, void*, int, hipStream_t);
-void fx_bias_gelu_fwd(int, int, const void*, const void*, void*, long, int, hipStream_t);
-void fx_bias_gelu_bwd(int, int, const void*, const void*, const void*, void*, float*, int, int, int,
-                      hipStream_t, int*, float*, void*, int);
-void fx_bias_dropout_add_fwd(int, const void*, const void*, const void*, void*, long, int, float,
-                             uint64_t, hipStream_t);
-void fx_dropout_bwd_colsum(int, const void*, void*, float*, int, int, int, float, uint64_t,
-                           hipStream_t, int*, float*, void*, int);
-void fx_dropout_fwd(int, const void*, void*, long, float, uint64_t, hipStream_t);
-void fx_ce_stats(int, const void*, const int64_t*, int, int, long, float*, float*, float*, int,
-                 hipStream_t);
-void fx_ce_bwd(int, const void*, void*, const int64_t*, const float*, const float*, int, int, long,
-               int, hipStream_t);
-int fx_sumsq_blocks(long n);
-void fx_sumsq_f32(const float*, long, float*, int, hipStream_t);
-void fx_sumsq_16(int, const void*, long, float*, int, hipStream_t);
-void fx_sumsq_chunks(const int64_t*, const int64_t*, int, float*, hipStream_t);
-void fx_adamw_tune(int, int, int);
-void fx_adamw_flat(int, float*, const float*, float*, float*, void*, long, float, float, float,
-                   float, float, float, const float*, const int*, const int*, hipStream_t);
-void fx_adamw_flat_g16(int, float*, const void*, float*, float*, void*, long, float, float,
-                       float, float, float, float, const float*, const int*, const int*,
-                       hipStream_t);
-int fx_adamw_flat_pk(int, void*, const void*, float*, float*, void*, long, float, float, float,
-                     float, float, float, const float*, const int*, const int*, hipStream_t);
-int fx_adamw_flat_pk_g16(int, void*, const void*, float*, float*, void*, long, float, float,
-                         float, float, float, float, const float*, const int*, const int*,
-                         hipStream_t);
-void fx_pk_split(const float*, void*, void*, long, hipStream_t);
-void fx_pk_join(const void*, const void*, float*, long, hipStream_t);
-void fx_cast_f32(int, const float*, void*, long, hipStream_t);
-void fx_accum_f32(int, float*, const void*, long, int, hipStream_t);
-void fx_embedding_fwd(int, const int64_t*, const int64_t*, const void*, const void*, void*, int,
-                      int, long, long, hipStream_t);
-void fx_embedding_bwd(int, const int64_t*, const void*, float*, int, int, long, long,
-                      hipStream_t);
-void fx_fa_set_dkdv64(int);
-void fx_fa_set_dq64(int);
-void fx_fa_set_dkdv_vreg(int);
-int fx_fa_lab();
-int fx_fa_set_stamps(void*);
-int fx_flash_fwd(int, const void*, const void*, const void*, void*, float*, const long*, const long*,
-                 const long*, const long*, const int*, const float*, long, int, int, int, int, int,
-                 int, float, float, uint64_t, hipStream_t);
-int fx_flash_bwd(int, const void*, const void*, const void*, const void*, const void*, const float*,
-                 float*, void*, void*, void*, const long*, const long*, const long*, const long*,
-                 const long*, const long*, const int*, const float*, long, int, int, int, int, int,
-                 int, float, float, uint64_t, hipStream_t);
-int fx_fake_quant_fwd(int, const void*, void*, const float*, int, long, hipStream_t);
-void fx_absmax(int, const void*, long, float*, hipStream_t);
-int fx_gn_nseg(long, long);
-int fx_gn_fwd(int, const void*, const float*, const float*, const float*, const float*, void*,
-              double*, float*, float*, int, int, int, long, int, float, int, hipStream_t);
-int fx_gn_bwd_reduce(int, const void*, const void*, const float*, const float*, const float*,
-                     const float*, const float*, const float*, float*, int, int, int, long, int,
-                     int, hipStream_t);
-int fx_gn_bwd_apply(int, const void*, const void*, const float*, const float*, const float*,
-                    const float*, const float*, const float*, const float*, const float*, void*,
-                    int, int, int, long, int, int, hipStream_t);
-int fx_transpose16(int, const void*, void*, float*, int, int, long, long, hipStream_t);
-int fx_sample(int, const void*, long, int, int, float, int, float, const float*, int64_t*, float*,
-              float*, hipStream_t);
-int fx_decode_attn(int, const void*, const void*, const void*, void*, const int*, int, int, int,
-                   int, int, float*, long, long, long, long, long, long, float, hipStream_t);
-void fx_embedding_bwd_sorted(int, const int64_t*, const int64_t*, const void*, float*, int, int,
-                             long, long, hipStream_t);
-int fx_softmax_fwd(int, int, const void*, const void*, void*, long, int, int, long, float, int,
-                   hipStream_t);
-int fx_softmax_bwd(int, const void*, const void*, void*, long, int, int, float, int, hipStream_t);
-int fx_gemm(int, int, int, int, int, int, int, const void*, long, const void*, long, void*, long,
-            const void*, void*, long, int, hipStream_t, float*, float*);
-long fx_gemm_ws_bytes(int, int, int, int);
-void fx_gemm_set_gm(int);
-void fx_gemm_set_geom(int, int);
-int fx_gemm_tuned(long*, int);
-void fx_gemm_set_tuned(int, int, int, int, int, int, int);
-void fx_gemm_set_tune(int);
-void fx_gemm_set_persist(int);
-void fx_gemm_set_xrect(int);
-int fx_decode_gemv(int, int, int, int, int, const void*, long, const void*, long, const void*,
-                   const void*, long, void*, long, void*, void*, const long*, int, int, int,
-                   const void*, const void*, float, hipStream_t);
-void fx_set_dropout_salt(const void*);
-hipStream_t fx_cumask_stream_create(int, int*);
-int fx_stream_destroy(hipStream_t);
-void fx_set_adamw_lr_ptr(const void*);
-int fx_comm_max_world();
-int fx_comm_max_blocks();
-void* fx_comm_alloc(long);
-int fx_comm_free(void*);
-int fx_comm_ipc_handle(void*, char*);
-void* fx_comm_ipc_open(const char*);
-int fx_comm_ipc_close(void*);
-int fx_comm_allreduce(int, int, const void*, void*, long, int, int, const uint64_t*, unsigned int*,
-                      unsigned int*, long, unsigned long long, hipStream_t);
-}
+#include "fx_api.h"
 
 #define P(x) reinterpret_cast<void*>(x)
 #define CP(x) reinterpret_cast<const void*>(x)
@@ -138,14 +30,14 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("coltile_splits", &fx_coltile_splits);
   m.def("add_ln_fwd", [](int dt, ptr x, ptr bias, ptr res, ptr g, ptr b, ptr s_out, ptr y,
                          ptr mean, ptr rstd, int rows, int h, float eps, float p, uint64_t key,
-                         ptr st) {
+                         ptr salt, ptr st) {
     fx_add_ln_fwd(dt, CP(x), CP(bias), CP(res), CP(g), CP(b), P(s_out), P(y), F(mean), F(rstd),
-                  rows, h, eps, p, key, S(st));
+                  rows, h, eps, p, key, CP(salt), S(st));
   });
   m.def("ln_bwd_row", [](int dt, ptr dy, ptr s, ptr mean, ptr rstd, ptr g, ptr ds_in, ptr ds_out,
-                         ptr dx_out, int rows, int h, float p, uint64_t key, ptr st) {
+                         ptr dx_out, int rows, int h, float p, uint64_t key, ptr salt, ptr st) {
     fx_ln_bwd_row(dt, CP(dy), CP(s), F(mean), F(rstd), CP(g), CP(ds_in), P(ds_out), P(dx_out),
-                  rows, h, p, key, S(st));
+                  rows, h, p, key, CP(salt), S(st));
   });
   // LayerNorm backward with dgamma / dbeta (/ dbias of the fused residual's
   // linear) column sums in the same pass; returns -1 if h is not covered
@@ -153,16 +45,16 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("ln_bwd_cols", [](int dt, ptr dy, ptr s, ptr mean, ptr rstd, ptr g, ptr ds_in, ptr ds_out,
                           ptr dx_out, int rows, int h, float p, uint64_t key, ptr part,
                           int with_dbias, ptr fg, ptr tg, int accg, ptr fb, ptr tb, int accb,
-                          ptr fx, ptr tx, int accx, ptr st) {
+                          ptr fx, ptr tx, int accx, ptr salt, ptr st) {
     return fx_ln_bwd_cols(dt, CP(dy), CP(s), F(mean), F(rstd), CP(g), CP(ds_in), P(ds_out),
                           P(dx_out), rows, h, p, key, F(part), with_dbias, F(fg), P(tg), accg,
-                          F(fb), P(tb), accb, F(fx), P(tx), accx, S(st));
+                          F(fb), P(tb), accb, F(fx), P(tx), accx, CP(salt), S(st));
   }, py::arg("dt"), py::arg("dy"), py::arg("s"), py::arg("mean"), py::arg("rstd"), py::arg("g"),
      py::arg("ds_in"), py::arg("ds_out"), py::arg("dx_out"), py::arg("rows"), py::arg("h"),
      py::arg("p"), py::arg("key"), py::arg("part"), py::arg("with_dbias"), py::arg("fg") = 0,
      py::arg("tg") = 0, py::arg("accg") = 0, py::arg("fb") = 0, py::arg("tb") = 0,
      py::arg("accb") = 0, py::arg("fx") = 0, py::arg("tx") = 0, py::arg("accx") = 0,
-     py::arg("st") = 0);
+     py::arg("salt") = 0, py::arg("st") = 0);
   // column-sum producers: cnt != 0 fuses the finalize (last workgroup of a
   // column tile sums the splits into f*/t* outputs); cnt == 0: the caller
   // runs coltile_finalize
@@ -192,19 +84,22 @@ PYBIND11_MODULE(_kernels, m) {
      py::arg("part"), py::arg("rows"), py::arg("cols"), py::arg("splits"), py::arg("st"),
      py::arg("cnt") = 0, py::arg("out_f32") = 0, py::arg("out_t") = 0, py::arg("acc") = 0);
   m.def("bias_dropout_add_fwd", [](int dt, ptr x, ptr bias, ptr res, ptr out, long n, int cols,
-                                   float p, uint64_t key, ptr st) {
-    fx_bias_dropout_add_fwd(dt, CP(x), CP(bias), CP(res), P(out), n, cols, p, key, S(st));
+                                   float p, uint64_t key, ptr salt, ptr st) {
+    fx_bias_dropout_add_fwd(dt, CP(x), CP(bias), CP(res), P(out), n, cols, p, key, CP(salt),
+                            S(st));
   });
   m.def("dropout_bwd_colsum", [](int dt, ptr dout, ptr dx, ptr part, int rows, int cols,
-                                 int splits, float p, uint64_t key, ptr st, ptr cnt, ptr out_f32,
-                                 ptr out_t, int acc) {
-    fx_dropout_bwd_colsum(dt, CP(dout), P(dx), F(part), rows, cols, splits, p, key, S(st),
+                                 int splits, float p, uint64_t key, ptr salt, ptr st, ptr cnt,
+                                 ptr out_f32, ptr out_t, int acc) {
+    fx_dropout_bwd_colsum(dt, CP(dout), P(dx), F(part), rows, cols, splits, p, key, CP(salt), S(st),
                           reinterpret_cast<int*>(cnt), F(out_f32), P(out_t), acc);
   }, py::arg("dt"), py::arg("dout"), py::arg("dx"), py::arg("part"), py::arg("rows"),
-     py::arg("cols"), py::arg("splits"), py::arg("p"), py::arg("key"), py::arg("st"),
-     py::arg("cnt") = 0, py::arg("out_f32") = 0, py::arg("out_t") = 0, py::arg("acc") = 0);
-  m.def("dropout_fwd", [](int dt, ptr x, ptr y, long n, float p, uint64_t key, ptr st) {
-    fx_dropout_fwd(dt, CP(x), P(y), n, p, key, S(st));
+     py::arg("cols"), py::arg("splits"), py::arg("p"), py::arg("key"), py::arg("salt"),
+     py::arg("st"), py::arg("cnt") = 0, py::arg("out_f32") = 0, py::arg("out_t") = 0,
+     py::arg("acc") = 0);
+  m.def("dropout_fwd", [](int dt, ptr x, ptr y, long n, float p, uint64_t key, ptr salt,
+                          ptr st) {
+    fx_dropout_fwd(dt, CP(x), P(y), n, p, key, CP(salt), S(st));
   });
   m.def("ce_stats", [](int dt, ptr logits, ptr labels, int rows, int V, long vstart, ptr mx,
                        ptr sm, ptr tg, int ignore, ptr st) {
@@ -227,34 +122,15 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("sumsq_16", [](int dt, ptr x, long n, ptr partial, int blocks, ptr st) {
     fx_sumsq_16(dt, CP(x), n, F(partial), blocks, S(st));
   });
-  m.def("adamw_tune", &fx_adamw_tune, py::arg("grid"), py::arg("nt"), py::arg("wide") = 0);
-  m.def("adamw_flat", [](int dt, ptr p, ptr g, ptr mm, ptr vv, ptr p16, long n, float lr,
-                         float b1, float b2, float eps, float wd, float l2, ptr gscale, ptr skip,
-                         ptr step, ptr st) {
-    fx_adamw_flat(dt, F(p), F(g), F(mm), F(vv), P(p16), n, lr, b1, b2, eps, wd, l2, F(gscale),
-                  reinterpret_cast<const int*>(skip), reinterpret_cast<const int*>(step), S(st));
-  });
-  m.def("adamw_flat_g16", [](int dt, ptr p, ptr g, ptr mm, ptr vv, ptr p16, long n, float lr,
-                             float b1, float b2, float eps, float wd, float l2, ptr gscale,
-                             ptr skip, ptr step, ptr st) {
-    fx_adamw_flat_g16(dt, F(p), CP(g), F(mm), F(vv), P(p16), n, lr, b1, b2, eps, wd, l2,
-                      F(gscale), reinterpret_cast<const int*>(skip),
-                      reinterpret_cast<const int*>(step), S(st));
-  });
-  // packed master: p = the master's low halves, p16 = the bf16 parameters (high halves)
-  m.def("adamw_flat_pk", [](int dt, ptr p, ptr g, ptr mm, ptr vv, ptr p16, long n, float lr,
-                            float b1, float b2, float eps, float wd, float l2, ptr gscale,
-                            ptr skip, ptr step, ptr st) {
-    return fx_adamw_flat_pk(dt, P(p), CP(g), F(mm), F(vv), P(p16), n, lr, b1, b2, eps, wd, l2,
-                            F(gscale), reinterpret_cast<const int*>(skip),
-                            reinterpret_cast<const int*>(step), S(st));
-  });
-  m.def("adamw_flat_pk_g16", [](int dt, ptr p, ptr g, ptr mm, ptr vv, ptr p16, long n, float lr,
-                                float b1, float b2, float eps, float wd, float l2, ptr gscale,
-                                ptr skip, ptr step, ptr st) {
-    return fx_adamw_flat_pk_g16(dt, P(p), CP(g), F(mm), F(vv), P(p16), n, lr, b1, b2, eps, wd,
-                                l2, F(gscale), reinterpret_cast<const int*>(skip),
-                                reinterpret_cast<const int*>(step), S(st));
+  // flags: bit 0 = 16-bit gradient, bit 1 = packed master (p = the master's low halves,
+  // p16 = the bf16 parameters); lr_dev: device learning rate (0 = lr); grid / nt / wide: the
+  // launch shape (loss_optim_embed.hip fx_adamw)
+  m.def("adamw", [](int dt, int flags, ptr p, ptr g, ptr mm, ptr vv, ptr p16, long n, float lr,
+                    float b1, float b2, float eps, float wd, float l2, ptr gscale, ptr skip,
+                    ptr step, ptr lr_dev, int grid, int nt, int wide, ptr st) {
+    return fx_adamw(dt, flags, P(p), CP(g), F(mm), F(vv), P(p16), n, lr, b1, b2, eps, wd, l2,
+                    F(gscale), reinterpret_cast<const int*>(skip),
+                    reinterpret_cast<const int*>(step), F(lr_dev), grid, nt, wide, S(st));
   });
   m.def("pk_split", [](ptr x, ptr hi, ptr lo, long n, ptr st) {
     fx_pk_split(F(x), P(hi), P(lo), n, S(st));
@@ -293,23 +169,23 @@ PYBIND11_MODULE(_kernels, m) {
   m.def("flash_fwd", [](int dt, ptr q, ptr k, ptr v, ptr out, ptr lse, std::vector<long> qs,
                         std::vector<long> ks, std::vector<long> vs, std::vector<long> os,
                         ptr kv_lens, ptr kbias, long kb_stride, int B, int H, int Sq, int Sk, int D,
-                        int causal, float scale, float p, uint64_t key, ptr st) {
+                        int causal, float scale, float p, uint64_t key, ptr salt, ptr st) {
     auto a = v3(qs), b = v3(ks), c = v3(vs), d = v3(os);
     return fx_flash_fwd(dt, CP(q), CP(k), CP(v), P(out), F(lse), a.data(), b.data(), c.data(),
                         d.data(), reinterpret_cast<const int*>(kv_lens), F(kbias), kb_stride, B, H,
-                        Sq, Sk, D, causal, scale, p, key, S(st));
+                        Sq, Sk, D, causal, scale, p, key, CP(salt), S(st));
   });
   m.def("flash_bwd", [](int dt, ptr q, ptr k, ptr v, ptr o, ptr dout, ptr lse, ptr delta, ptr dq,
                         ptr dk,
                         ptr dv, std::vector<long> qs, std::vector<long> ks, std::vector<long> vs,
                         std::vector<long> os, std::vector<long> dqs, std::vector<long> dks,
                         ptr kv_lens, ptr kbias, long kb_stride, int B, int H, int Sq, int Sk, int D,
-                        int causal, float scale, float p, uint64_t key, ptr st) {
+                        int causal, float scale, float p, uint64_t key, ptr salt, ptr st) {
     auto a = v3(qs), b = v3(ks), c = v3(vs), d = v3(os), e = v3(dks), f = v3(dqs);
     return fx_flash_bwd(dt, CP(q), CP(k), CP(v), CP(o), CP(dout), F(lse), F(delta), P(dq), P(dk),
                         P(dv), a.data(), b.data(), c.data(), d.data(), f.data(), e.data(),
                         reinterpret_cast<const int*>(kv_lens), F(kbias), kb_stride, B, H, Sq, Sk,
-                        D, causal, scale, p, key, S(st));
+                        D, causal, scale, p, key, CP(salt), S(st));
   });
   m.def("gn_nseg", [](long rows, long hw) { return fx_gn_nseg(rows, hw); });
   m.def("gn_fwd", [](int dt, ptr x, ptr gamma, ptr beta, ptr scale, ptr shift, ptr y, ptr part,
@@ -396,9 +272,6 @@ PYBIND11_MODULE(_kernels, m) {
     return py::make_tuple(reinterpret_cast<ptr>(s), got);
   });
   m.def("stream_destroy", [](ptr s) { return fx_stream_destroy(S(s)); });
-  // graph mode: device-resident dropout salt / AdamW learning rate (0 = off)
-  m.def("set_dropout_salt", [](ptr p) { fx_set_dropout_salt(CP(p)); });
-  m.def("set_adamw_lr_ptr", [](ptr p) { fx_set_adamw_lr_ptr(CP(p)); });
   // intra-node one-shot all-reduce over IPC-mapped peer memory (comm.hip)
   m.def("comm_max_world", &fx_comm_max_world);
   m.def("comm_max_blocks", &fx_comm_max_blocks);

@@ -37,6 +37,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fx_api.h"
 #include "fx_common.h"
 
 namespace {

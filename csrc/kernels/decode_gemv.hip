@@ -35,6 +35,7 @@
 
 #include <type_traits>
 
+#include "fx_api.h"
 #include "fx_common.h"
 
 namespace {

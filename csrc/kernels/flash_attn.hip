@@ -27,6 +27,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "fx_api.h"
 #include "fx_common.h"
 
 typedef short v4s __attribute__((ext_vector_type(4)));
@@ -344,7 +345,7 @@ struct AttnParams {
   uint32_t klo, khi, thr;
   float drop_scale;
   int dval;              // valid head dim (<= the tile's D; columns past it are zero)
-  const uint64_t* salt;  // graph mode: per-replay device salt (fx_set_dropout_salt)
+  const uint64_t* salt;  // graph mode: per-replay device salt (the launchers' salt argument)
   int pair;              // causal forward: two query blocks per workgroup (fa_fwd_kernel)
   int row16;             // output rows 16-byte aligned (store_row16's 16-byte stores)
 };
@@ -1195,7 +1196,7 @@ __global__ __launch_bounds__(64 * NW, 2) void fa_bwd_dkdv_q64v_kernel(AttnParams
 
 AttnParams make_params(const void* q, const void* k, const void* v, const long* qs,
                        const long* ks, const long* vs, int B, int H, int Sq, int Sk, float scale,
-                       float p, uint64_t key) {
+                       float p, uint64_t key, const void* salt) {
   AttnParams P{};
   P.q = (const uint16_t*)q;
   P.k = (const uint16_t*)k;
@@ -1209,7 +1210,7 @@ AttnParams make_params(const void* q, const void* k, const void* v, const long* 
   P.khi = (uint32_t)(key >> 32);
   P.thr = (uint32_t)(p * 65536.0f + 0.5f);
   P.drop_scale = p < 1.f ? 1.f / (1.f - p) : 0.f;
-  P.salt = p > 0.f ? g_fx_dropout_salt : nullptr;
+  P.salt = p > 0.f ? reinterpret_cast<const uint64_t*>(salt) : nullptr;
   return P;
 }
 
@@ -1357,12 +1358,12 @@ static int flash_fwd_t(const void* q, const void* k, const void* v, void* out, f
                             const long* qs, const long* ks, const long* vs, const long* os,
                             const int* kv_lens, const float* kbias, long kb_stride, int B, int H,
                             int Sq, int Sk, int D, int causal, float scale, float p, uint64_t key,
-                            hipStream_t st) {
+                            const void* salt, hipStream_t st) {
   // D is the head dim of the tensors; the kernel runs the smallest tile width
   // >= D (64 / 96 / 128) with the columns past D read as zeros
   if (D % 8 || D <= 0 || D > 128) return -1;
   if (kbias && (causal || kb_stride < ((Sk + 127) / 128) * 128)) return -2;
-  AttnParams P = make_params(q, k, v, qs, ks, vs, B, H, Sq, Sk, scale, p, key);
+  AttnParams P = make_params(q, k, v, qs, ks, vs, B, H, Sq, Sk, scale, p, key, salt);
   P.dval = D;
   D = tile_dim(D);
   P.out = (uint16_t*)out;
@@ -1398,10 +1399,10 @@ static int flash_bwd_t(const void* q, const void* k, const void* v, const void* 
                             const long* os, const long* dqs, const long* dks, const int* kv_lens,
                             const float* kbias, long kb_stride, int B, int H,
                             int Sq, int Sk, int D, int causal, float scale, float p, uint64_t key,
-                            hipStream_t st) {
+                            const void* salt, hipStream_t st) {
   if (D % 8 || D <= 0 || D > 128) return -1;
   if (kbias && (causal || kb_stride < ((Sk + 127) / 128) * 128)) return -2;
-  AttnParams P = make_params(q, k, v, qs, ks, vs, B, H, Sq, Sk, scale, p, key);
+  AttnParams P = make_params(q, k, v, qs, ks, vs, B, H, Sq, Sk, scale, p, key, salt);
   P.dval = D;
   D = tile_dim(D);
   P.o = (const uint16_t*)o;
@@ -1473,13 +1474,14 @@ extern "C" int fx_flash_fwd(int dt, const void* q, const void* k, const void* v,
                             float* lse, const long* qs, const long* ks, const long* vs,
                             const long* os, const int* kv_lens, const float* kbias,
                             long kb_stride, int B, int H, int Sq, int Sk, int D, int causal,
-                            float scale, float p, uint64_t key, hipStream_t st) {
+                            float scale, float p, uint64_t key, const void* salt,
+                            hipStream_t st) {
   if (dt == 0)
     return flash_fwd_t<bf16>(q, k, v, out, lse, qs, ks, vs, os, kv_lens, kbias, kb_stride, B, H,
-                             Sq, Sk, D, causal, scale, p, key, st);
+                             Sq, Sk, D, causal, scale, p, key, salt, st);
   if (dt == 1)
     return flash_fwd_t<f16>(q, k, v, out, lse, qs, ks, vs, os, kv_lens, kbias, kb_stride, B, H,
-                            Sq, Sk, D, causal, scale, p, key, st);
+                            Sq, Sk, D, causal, scale, p, key, salt, st);
   return -3;
 }
 
@@ -1489,14 +1491,14 @@ extern "C" int fx_flash_bwd(int dt, const void* q, const void* k, const void* v,
                             const long* os, const long* dqs, const long* dks, const int* kv_lens,
                             const float* kbias, long kb_stride, int B, int H, int Sq, int Sk,
                             int D, int causal, float scale, float p, uint64_t key,
-                            hipStream_t st) {
+                            const void* salt, hipStream_t st) {
   if (dt == 0)
     return flash_bwd_t<bf16>(q, k, v, o, dout, lse, delta, dq, dk, dv, qs, ks, vs, os, dqs, dks,
                              kv_lens, kbias, kb_stride, B, H, Sq, Sk, D, causal, scale, p, key,
-                             st);
+                             salt, st);
   if (dt == 1)
     return flash_bwd_t<f16>(q, k, v, o, dout, lse, delta, dq, dk, dv, qs, ks, vs, os, dqs, dks,
                             kv_lens, kbias, kb_stride, B, H, Sq, Sk, D, causal, scale, p, key,
-                            st);
+                            salt, st);
   return -3;
 }

@@ -101,7 +101,6 @@ __host__ __device__ __forceinline__ uint64_t fx_mix64(uint64_t z) {
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   return z ^ (z >> 31);
 }
-extern const uint64_t* g_fx_dropout_salt;  // host-side, set by fx_set_dropout_salt
 __device__ __forceinline__ uint64_t salt_key(uint64_t key, uint64_t salt) {
   return fx_mix64(key ^ fx_mix64(salt + 0x9E3779B97F4A7C15ull)) & 0x7FFFFFFFFFFFFFFFull;
 }

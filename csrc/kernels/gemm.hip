@@ -25,6 +25,7 @@
 #include <tuple>
 #include <vector>
 
+#include "fx_api.h"
 #include "fx_common.h"
 #include "gemm_common.h"
 

@@ -20,6 +20,7 @@
 //  bwd K4 gn_bwd_apply : dx = rstd*(k*dz - g1 - xhat*g2), k = gamma*(1+scale)
 // Every element pass is a single streaming read (K1, K3) or read+write (K2,
 // K4) of 16-bit data, 8 elements per lane when the row length allows.
+#include "fx_api.h"
 #include "fx_common.h"
 
 namespace {

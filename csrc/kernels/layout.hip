@@ -19,6 +19,7 @@
 // (part[tile_row][col]) -- the bias gradient of the GEMM whose dy is being
 // transposed, for free while the tile is in registers; coltile_finalize
 // reduces the tile rows.
+#include "fx_api.h"
 #include "fx_common.h"
 
 namespace {

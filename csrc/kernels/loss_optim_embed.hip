@@ -15,6 +15,7 @@
 //    fusion, reference P09), so an update is ONE launch per parameter group;
 //    the clip coefficient and found-inf flag are read from device memory, so
 //    the step never syncs the host.
+#include "fx_api.h"
 #include "fx_common.h"
 
 namespace {
@@ -564,98 +565,55 @@ extern "C" void fx_sumsq_f32(const float* x, long n, float* partial, int blocks,
   sumsq_f32_kernel<<<blocks, 256, 0, st>>>(x, n, partial);
 }
 
-static int g_adamw_grid = 0, g_adamw_nt = 1, g_adamw_wide = 0;  // tuning knobs
-static const float* g_adamw_lr = nullptr;     // graph mode: device learning rate
-extern "C" void fx_set_adamw_lr_ptr(const void* p) { g_adamw_lr = (const float*)p; }
-// grid: workgroup cap (0 = fill the chip); nt: non-temporal accesses;
-// wide: 1 = 1024-thread blocks with 4 float4 groups per thread (the capped,
-// forward-overlapped update), 0 = 256 x 2
-extern "C" void fx_adamw_tune(int grid, int nt, int wide) {
-  g_adamw_grid = grid;
-  g_adamw_nt = nt;
-  g_adamw_wide = wide;
+using AdamwKernel = void (*)(float*, const void*, float*, float*, uint16_t*, long, float, float,
+                             float, float, float, float, const float*, const int*, const int*,
+                             const float*);
+
+// The kernel instance of a launch shape: wide = 1024-thread blocks with 4
+// float4 groups per thread (the capped, forward-overlapped update; always
+// non-temporal), else 256 x 2 with (nt) or without non-temporal accesses.
+template <typename T, bool G16, bool PK>
+static AdamwKernel adamw_kernel(int nt, int wide) {
+  if (wide) return adamw_flat_kernel<T, true, 1024, 4, G16, PK>;
+  if (nt) return adamw_flat_kernel<T, true, 256, 2, G16, PK>;
+  return adamw_flat_kernel<T, false, 256, 2, G16, PK>;
 }
 
-template <typename T, bool NT, int BS, int U, bool G16 = false, bool PK = false>
-static void adamw_launch(float* p, const void* g, float* m, float* v, void* p16, long n,
-                         float lr, float beta1, float beta2, float eps, float wd, float l2,
-                         const float* gscale, const int* skip, const int* step, hipStream_t st) {
+// One AdamW update of a flat range; every launch carries its own shape and
+// learning-rate source (no state between calls).
+// flags bit 0: the gradient is stored in the model's 16-bit dtype; bit 1:
+// packed master (bf16 models only, else -1 and nothing is launched) --
+// `master` is the low-half array and `p16` the bf16 parameters (= the high
+// halves), read and written.  lr_dev: device learning rate (null = lr).
+// grid_cap: workgroup cap (0 = fill the chip).
+extern "C" int fx_adamw(int dtype, int flags, void* master, const void* grad, float* m, float* v,
+                        void* p16, long n, float lr, float beta1, float beta2, float eps,
+                        float wd, float l2, const float* gscale, const int* skip,
+                        const int* step, const float* lr_dev, int grid_cap, int nt, int wide,
+                        hipStream_t st) {
+  const bool g16 = flags & 1, pk = flags & 2;
+  if (pk && dtype != 0) return -1;
+  AdamwKernel kernel;
+  if (pk)
+    kernel = g16 ? adamw_kernel<bf16, true, true>(nt, wide)
+                 : adamw_kernel<bf16, false, true>(nt, wide);
+  else if (dtype == 0)
+    kernel = g16 ? adamw_kernel<bf16, true, false>(nt, wide)
+                 : adamw_kernel<bf16, false, false>(nt, wide);
+  else
+    kernel = g16 ? adamw_kernel<f16, true, false>(nt, wide)
+                 : adamw_kernel<f16, false, false>(nt, wide);
   // at most 8 resident 256-thread blocks per CU (2 of 1024)
+  const int BS = wide ? 1024 : 256, U = wide ? 4 : 2;
   const long per = (long)BS * U * 4;
-  long blocks = (n + per - 1) / per;
+  const long blocks = (n + per - 1) / per;
   const long cap = 256L * (8 * 256 / BS) * 4;
   int grid = (int)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
-  if (g_adamw_grid > 0 && g_adamw_grid < grid) grid = g_adamw_grid;
-  adamw_flat_kernel<T, NT, BS, U, G16, PK><<<grid, BS, 0, st>>>(p, g, m, v, (uint16_t*)p16, n, lr, beta1,
-                                                      beta2, eps, wd, l2, gscale, skip, step,
-                                                      g_adamw_lr);
+  if (grid_cap > 0 && grid_cap < grid) grid = grid_cap;
+  kernel<<<grid, BS, 0, st>>>((float*)master, grad, m, v, (uint16_t*)p16, n, lr, beta1, beta2, eps,
+                              wd, l2, gscale, skip, step, lr_dev);
+  return 0;
 }
-
-extern "C" void fx_adamw_flat(int dtype, float* p, const float* g, float* m, float* v, void* p16,
-                              long n, float lr, float beta1, float beta2, float eps, float wd,
-                              float l2, const float* gscale, const int* skip, const int* step,
-                              hipStream_t st) {
-#define FX_ADAMW_ARGS p, g, m, v, p16, n, lr, beta1, beta2, eps, wd, l2, gscale, skip, step, st
-  if (g_adamw_wide) {
-    FX_DISPATCH_T(dtype, adamw_launch<T, true, 1024, 4>(FX_ADAMW_ARGS));
-  } else if (g_adamw_nt) {
-    FX_DISPATCH_T(dtype, adamw_launch<T, true, 256, 2>(FX_ADAMW_ARGS));
-  } else {
-    FX_DISPATCH_T(dtype, adamw_launch<T, false, 256, 2>(FX_ADAMW_ARGS));
-  }
-#undef FX_ADAMW_ARGS
-}
-
-// the same with a 16-bit gradient (model dtype)
-extern "C" void fx_adamw_flat_g16(int dtype, float* p, const void* g, float* m, float* v,
-                                  void* p16, long n, float lr, float beta1, float beta2, float eps,
-                                  float wd, float l2, const float* gscale, const int* skip,
-                                  const int* step, hipStream_t st) {
-#define FX_ADAMW_ARGS p, g, m, v, p16, n, lr, beta1, beta2, eps, wd, l2, gscale, skip, step, st
-  if (g_adamw_wide) {
-    FX_DISPATCH_T(dtype, (adamw_launch<T, true, 1024, 4, true>(FX_ADAMW_ARGS)));
-  } else if (g_adamw_nt) {
-    FX_DISPATCH_T(dtype, (adamw_launch<T, true, 256, 2, true>(FX_ADAMW_ARGS)));
-  } else {
-    FX_DISPATCH_T(dtype, (adamw_launch<T, false, 256, 2, true>(FX_ADAMW_ARGS)));
-  }
-#undef FX_ADAMW_ARGS
-}
-
-// packed master (bf16 models only): `p` is the master's low-half array, `p16`
-// the bf16 parameters (= the high halves), read and written
-#define FX_ADAMW_PK(G16)                                                                     \
-  do {                                                                                       \
-    if (dtype != 0) return -1;                                                               \
-    if (g_adamw_wide)                                                                        \
-      adamw_launch<bf16, true, 1024, 4, G16, true>(FX_ADAMW_ARGS);                           \
-    else if (g_adamw_nt)                                                                     \
-      adamw_launch<bf16, true, 256, 2, G16, true>(FX_ADAMW_ARGS);                            \
-    else                                                                                     \
-      adamw_launch<bf16, false, 256, 2, G16, true>(FX_ADAMW_ARGS);                           \
-    return 0;                                                                                \
-  } while (0)
-extern "C" int fx_adamw_flat_pk(int dtype, void* lo, const void* g, float* m, float* v, void* hi,
-                                long n, float lr, float beta1, float beta2, float eps, float wd,
-                                float l2, const float* gscale, const int* skip, const int* step,
-                                hipStream_t st) {
-  float* p = (float*)lo;
-  void* p16 = hi;
-#define FX_ADAMW_ARGS p, g, m, v, p16, n, lr, beta1, beta2, eps, wd, l2, gscale, skip, step, st
-  FX_ADAMW_PK(false);
-#undef FX_ADAMW_ARGS
-}
-extern "C" int fx_adamw_flat_pk_g16(int dtype, void* lo, const void* g, float* m, float* v,
-                                    void* hi, long n, float lr, float beta1, float beta2,
-                                    float eps, float wd, float l2, const float* gscale,
-                                    const int* skip, const int* step, hipStream_t st) {
-  float* p = (float*)lo;
-  void* p16 = hi;
-#define FX_ADAMW_ARGS p, g, m, v, p16, n, lr, beta1, beta2, eps, wd, l2, gscale, skip, step, st
-  FX_ADAMW_PK(true);
-#undef FX_ADAMW_ARGS
-}
-#undef FX_ADAMW_PK
 
 // fp32 master <-> (bf16 parameter, low halves)
 extern "C" void fx_pk_split(const float* x, void* hi, void* lo, long n, hipStream_t st) {

@@ -12,6 +12,7 @@
 //  * column reductions (dgamma, dbeta, dbias) use a 128-column x 16-row
 //    tiling (256-byte row segments) with per-split fp32 partials and a tiny
 //    finalize kernel -- no float atomics, bitwise reproducible.
+#include "fx_api.h"
 #include "fx_common.h"
 
 namespace {
@@ -23,9 +24,10 @@ struct DropCfg {
   const uint64_t* salt;    // graph mode: per-replay device salt mixed into the key
 };
 
-// Graph mode (fx_set_dropout_salt): the key baked into a captured launch is
-// re-keyed on the device by the step salt, so every replay draws new masks
-// while forward, backward and recompute of one step agree.
+// Graph mode (the launchers' salt argument, a device uint64; null = eager
+// keys): the key baked into a captured launch is re-keyed on the device by
+// the step salt, so every replay draws new masks while forward, backward and
+// recompute of one step agree.
 __device__ __forceinline__ DropCfg resolve_drop(DropCfg d) {
   if (d.enabled && d.salt != nullptr) {
     const uint64_t k = salt_key(((uint64_t)d.khi << 32) | d.klo, *d.salt);
@@ -934,14 +936,14 @@ __global__ __launch_bounds__(256) void dropout_fwd_kernel(const uint16_t* __rest
     y[i] = Elt<T>::from_f(drop_apply(Elt<T>::to_f(x[i]), (uint64_t)i, drop));
 }
 
-DropCfg make_drop(float p, uint64_t key) {
+DropCfg make_drop(float p, uint64_t key, const void* salt) {
   DropCfg d;
   d.enabled = p > 0.f ? 1 : 0;
   d.klo = (uint32_t)(key & 0xffffffffu);
   d.khi = (uint32_t)(key >> 32);
   d.thr = (uint32_t)(p * 65536.0f + 0.5f);
   d.scale = p < 1.f ? 1.f / (1.f - p) : 0.f;
-  d.salt = g_fx_dropout_salt;
+  d.salt = reinterpret_cast<const uint64_t*>(salt);
   return d;
 }
 
@@ -999,8 +1001,8 @@ extern "C" int fx_coltile_splits(int rows, int cols) { return splits_for(rows, c
 extern "C" void fx_add_ln_fwd(int dtype, const void* x, const void* bias, const void* residual,
                               const void* gamma, const void* beta, void* s_out, void* y,
                               float* mean, float* rstd, int rows, int h, float eps, float p,
-                              uint64_t key, hipStream_t st) {
-  DropCfg d = make_drop(p, key);
+                              uint64_t key, const void* salt, hipStream_t st) {
+  DropCfg d = make_drop(p, key, salt);
   dim3 grid((rows + 3) / 4), block(256);
   auto X = (const uint16_t*)x;
   auto B = (const uint16_t*)bias;
@@ -1044,8 +1046,8 @@ extern "C" void fx_add_ln_fwd(int dtype, const void* x, const void* bias, const 
 extern "C" void fx_ln_bwd_row(int dtype, const void* dy, const void* s, const float* mean,
                               const float* rstd, const void* gamma, const void* ds_in,
                               void* ds_out, void* dx_out, int rows, int h, float p, uint64_t key,
-                              hipStream_t st) {
-  DropCfg d = make_drop(p, key);
+                              const void* salt, hipStream_t st) {
+  DropCfg d = make_drop(p, key, salt);
   dim3 grid((rows + 3) / 4), block(256);
   auto DY = (const uint16_t*)dy;
   auto S = (const uint16_t*)s;
@@ -1110,12 +1112,12 @@ extern "C" int fx_ln_bwd_cols(int dtype, const void* dy, const void* s, const fl
                               void* ds_out, void* dx_out, int rows, int h, float p, uint64_t key,
                               float* part, int with_dbias, float* fg, void* tg, int accg,
                               float* fb, void* tb, int accb, float* fx, void* tx, int accx,
-                              hipStream_t st) {
+                              const void* salt, hipStream_t st) {
   const int G = fx_ln_bwd_cols_blocks(rows, h, 4096);
   if (G == 0) return -1;
   const int wpr = ln_cols_wpr(h), hw = h / wpr;
   const int rpg = ln_cols_rows_per_group(rows, h);
-  DropCfg d = make_drop(p, key);
+  DropCfg d = make_drop(p, key, salt);
   auto DY = (const uint16_t*)dy;
   auto S = (const uint16_t*)s;
   auto GM = (const uint16_t*)gamma;
@@ -1211,8 +1213,8 @@ extern "C" void fx_bias_gelu_bwd(int dtype, int erf, const void* dy, const void*
 
 extern "C" void fx_bias_dropout_add_fwd(int dtype, const void* x, const void* bias,
                                         const void* residual, void* out, long n, int cols, float p,
-                                        uint64_t key, hipStream_t st) {
-  DropCfg d = make_drop(p, key);
+                                        uint64_t key, const void* salt, hipStream_t st) {
+  DropCfg d = make_drop(p, key, salt);
   long n8 = n / 8;
   FX_DISPATCH_T(dtype, bias_dropout_add_fwd_kernel<T><<<grid_for(n8), 256, 0, st>>>(
                            (const uint16_t*)x, (const uint16_t*)bias, (const uint16_t*)residual,
@@ -1221,10 +1223,10 @@ extern "C" void fx_bias_dropout_add_fwd(int dtype, const void* x, const void* bi
 
 extern "C" void fx_dropout_bwd_colsum(int dtype, const void* dout, void* dx, float* part,
                                       int rows, int cols, int splits, float p, uint64_t key,
-                                      hipStream_t st, int* cnt, float* out_f32, void* out_t,
-                                      int acc) {
+                                      const void* salt, hipStream_t st, int* cnt,
+                                      float* out_f32, void* out_t, int acc) {
   const ColFin fin = make_fin(cnt, out_f32, out_t, acc, nullptr, nullptr, 0);
-  DropCfg d = make_drop(p, key);
+  DropCfg d = make_drop(p, key, salt);
   int rps = (rows + splits - 1) / splits;
   dim3 grid((cols + 127) / 128, splits), block(256);
   FX_DISPATCH_T(dtype, dropout_bwd_colsum_kernel<T><<<grid, block, 0, st>>>(
@@ -1232,16 +1234,9 @@ extern "C" void fx_dropout_bwd_colsum(int dtype, const void* dout, void* dx, flo
 }
 
 extern "C" void fx_dropout_fwd(int dtype, const void* x, void* y, long n, float p, uint64_t key,
-                               hipStream_t st) {
-  DropCfg d = make_drop(p, key);
+                               const void* salt, hipStream_t st) {
+  DropCfg d = make_drop(p, key, salt);
   long n8 = n / 8;
   FX_DISPATCH_T(dtype, dropout_fwd_kernel<T><<<grid_for(n8), 256, 0, st>>>(
                            (const uint16_t*)x, (uint16_t*)y, n, d));
-}
-
-// graph-mode dropout salt (see resolve_drop): a device uint64 read by every
-// dropout-bearing launch issued while it is set (nullptr = eager keys)
-const uint64_t* g_fx_dropout_salt = nullptr;
-extern "C" void fx_set_dropout_salt(const void* p) {
-  g_fx_dropout_salt = reinterpret_cast<const uint64_t*>(p);
 }

@@ -8,6 +8,7 @@
 //
 // Decode attention is memory bound (one query row per (batch, head)): split-K
 // over the cached keys (see decode_attn_split_kernel).
+#include "fx_api.h"
 #include "fx_common.h"
 
 namespace {

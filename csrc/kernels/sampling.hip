@@ -23,6 +23,7 @@
 // Every pass re-reads the row from global memory (a 50k-entry fp32 row is
 // 200 KB: L2-resident, larger than LDS); decode batches are small, so the
 // kernel is latency- not bandwidth-bound and one launch replaces ~15.
+#include "fx_api.h"
 #include "fx_common.h"
 
 namespace {

@@ -19,6 +19,7 @@
 // this is its minimum traffic; masked-out columns of a causal row are neither
 // read nor exponentiated (about half the reads of a square causal score
 // matrix).  Statistics are fp32; exp via the hardware exp2.
+#include "fx_api.h"
 #include "fx_common.h"
 
 namespace {

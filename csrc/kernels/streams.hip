@@ -13,6 +13,8 @@
 
 #include <vector>
 
+#include "fx_api.h"
+
 extern "C" {
 
 // Creates a stream restricted to `ncu` CUs of the current device (clamped to

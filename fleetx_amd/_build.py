@@ -67,7 +67,7 @@ def build_kernels(verbose=False, jobs=None):
     bsrc = os.path.join(kdir, "bindings.cpp")
     bobj = os.path.join(OBJ, "bindings.o")
     objs.append(bobj)
-    if _newer(bobj, [bsrc]):
+    if _newer(bobj, [bsrc] + headers):
         jobs_list.append([hipcc(), "-O2", "-std=c++17", "-fPIC", "-x", "c++", "-D__HIP_PLATFORM_AMD__"]
                          + _py_includes() + ["-I/opt/rocm/include", "-c", bsrc, "-o", bobj])
     with cf.ThreadPoolExecutor(max_workers=jobs or min(8, os.cpu_count() or 4)) as ex:

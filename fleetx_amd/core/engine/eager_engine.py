@@ -25,18 +25,17 @@ import contextlib
 import os
 import sys
 import time
-import weakref
 
 import numpy as np
 import torch
 import torch.distributed as dist
 
 from .basic_engine import BasicEngine
-from ...ops import _lib
 from ...optims import build_optimizer, build_lr_scheduler
 from ...parallel import comm as _comm
 from ...parallel import topology as topo
 from ...parallel.grad_buffer import FlatParamGradBuffer
+from ...parallel import rng
 from ...parallel.rng import get_rng_state_tracker
 from ...utils import checkpoint as ckpt
 from ...utils import env
@@ -44,19 +43,6 @@ from ...utils.log import logger
 from ...utils.profiler import phase
 
 _END = object()
-_GRAPH_PTR_OWNER = [None]  # id of the engine whose device salt / lr pointers are registered
-
-
-def _release_graph_ptrs(owner):
-    if _GRAPH_PTR_OWNER[0] != owner:
-        return
-    _GRAPH_PTR_OWNER[0] = None
-    try:
-        k = _lib.kernels()
-        k.set_dropout_salt(0)
-        k.set_adamw_lr_ptr(0)
-    except Exception:  # interpreter shutdown / library gone
-        pass
 
 
 class DynamicLossScaler:
@@ -369,21 +355,17 @@ class EagerEngine(BasicEngine):
         return True
 
     def _graph_setup(self):
-        k = _lib.kernels()
         self._graph_salt = torch.full((1,), getattr(self, "_graph_salt_resume", 0),
                                       dtype=torch.int64, device=self.device)
         self._graph_lr = torch.zeros(1, dtype=torch.float32, device=self.device)
         # deferred update (optimizer.defer_update): it runs one step later and
         # reads the learning rate of its own step, copied here by each body
         self._graph_lr_pending = torch.zeros(1, dtype=torch.float32, device=self.device)
-        k.set_dropout_salt(self._graph_salt.data_ptr())
-        k.set_adamw_lr_ptr((self._graph_lr_pending if self._defer_update() else
-                            self._graph_lr).data_ptr())
-        # the kernels read these process-global device pointers: clear them when
-        # this engine goes away (unless a newer engine has taken them over), so
-        # a later engine / optimizer never reads freed memory
-        _GRAPH_PTR_OWNER[0] = id(self)
-        weakref.finalize(self, _release_graph_ptrs, id(self))
+        # every dropout launch reads the salt registered here (weakly: it
+        # dies with this engine); the optimizer's launches read its own lr_dev
+        rng.set_device_salt(self._graph_salt)
+        self.optimizer.lr_dev = (self._graph_lr_pending if self._defer_update() else
+                                 self._graph_lr)
 
     def _defer_update(self):
         return bool(getattr(self.optimizer, "defer_update", False))

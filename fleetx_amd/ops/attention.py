@@ -81,7 +81,7 @@ class _FlashAttn(torch.autograd.Function):
                           _strides(q), _strides(k), _strides(v), _strides(out), _lib.ptr(kl),
                           _lib.ptr(kb), kb.shape[1] if kb is not None else 0,
                           B, H, Sq, Sk, D, int(causal), float(scale), float(p), key,
-                          _lib.stream())
+                          _rng.device_salt_ptr(), _lib.stream())
         if rc != 0:
             raise RuntimeError("flash_fwd failed (%d)" % rc)
         _lib.maybe_sync()
@@ -112,7 +112,7 @@ class _FlashAttn(torch.autograd.Function):
             _strides(q), _strides(k), _strides(v), _strides(out), _strides(dq), _strides(dk),
             _lib.ptr(kl), _lib.ptr(kb), kb.shape[1] if kb is not None else 0,
             B, H, Sq, Sk, D, int(ctx.causal), float(ctx.scale), float(ctx.p),
-            ctx.key, _lib.stream())
+            ctx.key, _rng.device_salt_ptr(), _lib.stream())
         if rc != 0:
             raise RuntimeError("flash_bwd failed (%d)" % rc)
         _lib.maybe_sync()

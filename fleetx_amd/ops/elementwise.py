@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 from .norm import _dropout_ref, col_sum, colsum_tickets
-from ..parallel import grad_sink as sink
+from ..parallel import grad_sink as sink, rng as _rng
 
 
 def _gelu_ref(x, erf):
@@ -133,7 +133,7 @@ class _BiasDropoutAdd(torch.autograd.Function):
             _lib.kernels().bias_dropout_add_fwd(_lib.dt_code(x.dtype), x.data_ptr(),
                                                 _lib.ptr(bias), _lib.ptr(residual),
                                                 out.data_ptr(), x.numel(), cols, float(p), key,
-                                                _lib.stream())
+                                                _rng.device_salt_ptr(), _lib.stream())
         else:
             # fp32 like the kernel: one rounding, at the store
             v = x.float() if bias is None else x.float() + bias.float()
@@ -167,13 +167,14 @@ class _BiasDropoutAdd(torch.autograd.Function):
                     db = torch.empty(cols, device=dout.device, dtype=dout.dtype)
                     fin = {"out_t": db.data_ptr()}
                 k.dropout_bwd_colsum(dc, dout.data_ptr(), dx.data_ptr() if ctx.p > 0 else 0,
-                                     part.data_ptr(), rows, cols, splits, float(ctx.p), ctx.key, st,
+                                     part.data_ptr(), rows, cols, splits, float(ctx.p), ctx.key,
+                                     _rng.device_salt_ptr(), st,
                                      cnt=colsum_tickets(dout.device, cols), **fin)
                 if fused:
                     sink.close_write(bias)
             elif ctx.p > 0:
                 k.dropout_fwd(dc, dout.data_ptr(), dx.data_ptr(), dout.numel(), float(ctx.p),
-                              ctx.key, st)
+                              ctx.key, _rng.device_salt_ptr(), st)
         else:
             dx = _dropout_ref(dout, ctx.p, ctx.key)
             db = None
@@ -193,7 +194,8 @@ def _dropout_apply(x, p, key):
     if _lib.vec8_ok(8, x):   # flat: the kernel has a scalar tail, any numel
         y = torch.empty_like(x)
         _lib.kernels().dropout_fwd(_lib.dt_code(x.dtype), x.data_ptr(), y.data_ptr(),
-                                   x.numel(), float(p), key, _lib.stream())
+                                   x.numel(), float(p), key, _rng.device_salt_ptr(),
+                                   _lib.stream())
         return y
     return _dropout_ref(x, p, key)
 

@@ -127,7 +127,7 @@ def _ln_bwd_cols(k, dc, dy, s, mean, rstd, weight, ctx, ds_in, ds, dx, rows, h):
     rc = k.ln_bwd_cols(dc, dy.data_ptr(), s.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
                        weight.data_ptr(), _lib.ptr(ds_in), ds.data_ptr(), dx.data_ptr(), rows, h,
                        float(ctx.p), ctx.key, part.data_ptr(), int(with_db), fg, tg, ag, fb, tb,
-                       ab, fx, tx, ax, _lib.stream())
+                       ab, fx, tx, ax, _rng.device_salt_ptr(), _lib.stream())
     if rc != 0:
         raise RuntimeError("ln_bwd_cols: shape rows=%d h=%d not covered" % (rows, h))
     for prm, (f32, _, _) in zip(prms, outs):
@@ -155,7 +155,7 @@ class _AddLayerNorm(torch.autograd.Function):
             k.add_ln_fwd(_lib.dt_code(x.dtype), x.data_ptr(), _lib.ptr(bias), _lib.ptr(residual),
                          weight.data_ptr(), lnbias.data_ptr(), _lib.ptr(s), y.data_ptr(),
                          mean.data_ptr(), rstd.data_ptr(), rows, h, float(eps), float(p), key,
-                         _lib.stream())
+                         _rng.device_salt_ptr(), _lib.stream())
             s_saved = s if s is not None else x
             if s is None and store_sum:
                 s = x
@@ -208,7 +208,7 @@ class _AddLayerNorm(torch.autograd.Function):
                 return dx, dbias, dres, dw, db, None, None, None, None
             k.ln_bwd_row(dc, dy.data_ptr(), s.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
                          weight.data_ptr(), _lib.ptr(ds_in), ds.data_ptr(), dx.data_ptr(), rows, h,
-                         float(ctx.p), ctx.key, _lib.stream())
+                         float(ctx.p), ctx.key, _rng.device_salt_ptr(), _lib.stream())
             direct = sink.fused(weight) and sink.fused(ctx.lnbias)
             (tw, dw), (tb, db) = (_col_target(prm, direct, h, dy) for prm in (weight, ctx.lnbias))
             _coltile(0, dy, (s.data_ptr(), mean.data_ptr(), rstd.data_ptr()), rows, h, [tw, tb])

@@ -8,7 +8,7 @@ path (K14) as used by ``eager_engine.py:425-445``.
 
 MI355X design: the optimizer works on the ranges of a
 :class:`~fleetx_amd.parallel.grad_buffer.FlatParamGradBuffer` -- master, m
-and v are flat fp32 tensors, one HIP ``adamw_flat`` launch per range (a
+and v are flat fp32 tensors, one HIP ``adamw`` launch per range (a
 handful per step, never one per parameter).  The global grad-norm is a
 squared-sum kernel per range + (mp / pp / sharding) all-reduces of ONE float;
 the clip coefficient and the fp16 found-inf flag stay on the device, so a
@@ -165,14 +165,6 @@ class FlatOptimizer:
             return [gs(s, e) for s, e, _ in self.ranges]
         g = self.buffer.grad_flat
         return [g[s:e] for s, e, _ in self.ranges]
-
-    def _adamw_fn(self, g):
-        """The fused AdamW launcher for a gradient of this storage dtype (and
-        the packed master layout)."""
-        k = _lib.kernels()
-        if self._lo is not None:
-            return k.adamw_flat_pk if g.dtype == torch.float32 else k.adamw_flat_pk_g16
-        return k.adamw_flat if g.dtype == torch.float32 else k.adamw_flat_g16
 
     def compute_grad_norm(self):
         """Global L2 norm over the data/model-parallel world (device scalar)."""
@@ -471,13 +463,36 @@ class FusedAdamW(FlatOptimizer):
             self.m = [torch.zeros(e - s, dtype=torch.float32, device=dev) for s, e, _ in self.ranges]
             self.v = [torch.zeros(e - s, dtype=torch.float32, device=dev) for s, e, _ in self.ranges]
 
+    # graph mode: a device fp32 tensor every launch of THIS optimizer reads its
+    # learning rate from (None: the host value passed to the launch)
+    lr_dev = None
+    _adamw_const = None
+
+    def _adamw_mode(self, g, category):
+        """``(flags, wd, l2)``; flags: bit 0 = 16-bit gradient, bit 1 = packed master.  AdamW
+        decays the weights (wd); Adam adds L2 to the gradient AFTER clipping / unscaling."""
+        flags = int(g.dtype != torch.float32) | (2 if self._lo is not None else 0)
+        wd = float(self.weight_decay if category.decay else 0.0)
+        return (flags, wd, 0.0) if self.decoupled else (flags, 0.0, wd)
+
+    def _adamw(self, mode, master, grad, m, v, p16, n, lr, shape=(0, 1, 0), st=None):
+        """One fused launch over ``n`` elements at these device addresses on stream
+        ``st`` (default: the current one); ``shape``: (workgroup cap, non-temporal, wide)."""
+        c = self._adamw_const
+        if c is None:  # the binding and the launch constants, looked up once
+            c = self._adamw_const = (
+                _lib.kernels().adamw, _lib.dt_code(self.buffer.param_flat.dtype),
+                self.gscale.data_ptr(), self.found_inf.data_ptr(), self.dev_step.data_ptr())
+        flags, wd, l2 = mode
+        if c[0](c[1], flags, master, grad, m, v, p16, n, lr, self.beta1, self.beta2, self.eps,
+                wd, l2, c[2], c[3], c[4], 0 if self.lr_dev is None else self.lr_dev.data_ptr(),
+                *shape, _lib.stream() if st is None else st) != 0:
+            raise RuntimeError("adamw: a packed master needs a bf16 model")
+
     def _update_overlapped(self, lr):
         """AdamW per unit (root first, then layer 0, 1, ...) on the side
         stream; an event per unit gates that unit's next forward."""
-        k = _lib.kernels()
         pf = self.buffer.param_flat
-        gf = self.buffer.grad_flat
-        dt = _lib.dt_code(pf.dtype)
         os_ = self._opt_stream
         os_.wait_stream(torch.cuda.current_stream())  # grads final, clip scale computed
         # Cap the overlapped update's workgroups: uncapped it fills every CU and
@@ -489,13 +504,15 @@ class FusedAdamW(FlatOptimizer):
         wide = int(os.environ.get("FLEETX_ADAMW_OVERLAP_WIDE", str(int(self.overlap_wide))))
         # non-temporal loads / stores (1, default: each byte is touched once per step)
         nt = int(os.environ.get("FLEETX_ADAMW_NT", "1"))
+        # without a cap (a CU-masked stream, or FLEETX_ADAMW_OVERLAP_GRID=0) the
+        # launches keep the default shape: nt and wide apply to a capped update only
+        shape = (grid, nt, wide) if grid > 0 else (0, 1, 0)
         # (running the first units -- embeddings, layer 0 -- uncapped because
         # they gate the first forward kernels measured neutral on 6.7B / 1.3B:
         # profiles/r3_adamw/head_ab.txt; every unit is capped)
-        head = 0
         if getattr(self, "_overlap_args", None) is None:
             # launch arguments per unit, built once (the flat buffers never
-            # move): the per-step host cost is then one bound call per range
+            # move): the per-step host cost is then one binding call per range
             # -- on the 1.3B model slicing every view each step kept the GPU
             # waiting ~1.5 ms per step for the next forward
             units = []
@@ -506,34 +523,23 @@ class FusedAdamW(FlatOptimizer):
                     s, e, c = self.ranges[ri]
                     a, b = lo - s, hi - s
                     g = gviews[ri][a:b]
-                    wd = float(self.weight_decay if c.decay else 0.0)
-                    # AdamW: decoupled decay; Adam: L2 term (as in _update)
-                    wd_dec, l2 = (wd, 0.0) if self.decoupled else (0.0, wd)
-                    args.append((self._adamw_fn(g), self._mslice(ri, a, b).data_ptr(), g.data_ptr(),
-                                 self.m[ri][a:b].data_ptr(), self.v[ri][a:b].data_ptr(),
-                                 pf[lo:hi].data_ptr(), hi - lo, wd_dec, l2))
+                    args.append((self._adamw_mode(g, c), self._mslice(ri, a, b).data_ptr(),
+                                 g.data_ptr(), self.m[ri][a:b].data_ptr(),
+                                 self.v[ri][a:b].data_ptr(), pf[lo:hi].data_ptr(), hi - lo))
                 units.append((u, args))
             self._overlap_args = units
-            self._overlap_dev = (self.gscale.data_ptr(), self.found_inf.data_ptr(),
-                                 self.dev_step.data_ptr())
-        gs, fi, ds = self._overlap_dev
         lr = float(lr)
-        b1, b2, eps = self.beta1, self.beta2, self.eps
         with torch.cuda.stream(os_):
             st = _lib.stream()
-            for i, (u, args) in enumerate(self._overlap_args):
-                if grid and i == head:
-                    k.adamw_tune(grid, nt, wide)
-                for adamw, mp, gp, m1, v1, pp, n, wd, l2 in args:
-                    adamw(dt, mp, gp, m1, v1, pp, n, lr, b1, b2, eps, wd, l2, gs, fi, ds, st)
+            for u, args in self._overlap_args:
+                for a in args:
+                    self._adamw(*a, lr, shape, st)
                 if self._overlap_gather:  # ZeRO: this bucket's gather follows its update
                     self.buffer.gather_bucket_async(u)
                     continue
                 ev = torch.cuda.Event()
                 ev.record(os_)
                 self._unit_events[u] = ev
-        if grid:
-            k.adamw_tune(0, 1, 0)
 
     def _update_offloaded(self, lr):
         """Stream host-resident master/m/v through the GPU in chunks: the H2D
@@ -541,7 +547,6 @@ class FusedAdamW(FlatOptimizer):
         while the fused AdamW kernel updates chunk j (reference
         ``group_sharded_parallel(offload=True)``, ``eager_engine.py:236-242``).
         PCIe traffic: 24 B per parameter per step."""
-        k = _lib.kernels()
         cur = torch.cuda.current_stream()
         cs = self._copy_stream
         pf = self.buffer.param_flat
@@ -565,15 +570,11 @@ class FusedAdamW(FlatOptimizer):
         for j, (ri, o, n) in enumerate(jobs):
             nxt = upload(j + 1) if j + 1 < len(jobs) else None
             s, e, c = self.ranges[ri]
-            wd = self.weight_decay if c.decay else 0.0
             st = self._stage[j % 2]
             cur.wait_event(ready)
-            self._adamw_fn(gviews[ri])(_lib.dt_code(pf.dtype), st[0].data_ptr(),
-                                       gviews[ri][o:o + n].data_ptr(),
-                         st[1].data_ptr(), st[2].data_ptr(), pf[s + o:s + o + n].data_ptr(), n,
-                         float(lr), self.beta1, self.beta2, self.eps, float(wd), 0.0,
-                         self.gscale.data_ptr(), self.found_inf.data_ptr(),
-                         self.dev_step.data_ptr(), _lib.stream())
+            g = gviews[ri][o:o + n]  # (decoupled only, see _update: mode = (flags, wd, 0.0))
+            self._adamw(self._adamw_mode(g, c), st[0].data_ptr(), g.data_ptr(), st[1].data_ptr(),
+                        st[2].data_ptr(), pf[s + o:s + o + n].data_ptr(), n, float(lr))
             done = torch.cuda.Event()
             done.record(cur)
             with torch.cuda.stream(cs):
@@ -593,19 +594,13 @@ class FusedAdamW(FlatOptimizer):
         masters = [self._mslice(ri, 0, e - s) for ri, (s, e, _) in enumerate(self.ranges)]
         for (s, e, c), g, p, m, v in zip(self.ranges, self.grad_views(), masters, self.m,
                                          self.v):
-            wd = self.weight_decay if c.decay else 0.0
-            # AdamW: decoupled decay on the weights; Adam: L2 term added to the
-            # gradient AFTER clipping / loss-scale unscaling
-            wd_dec, l2 = (wd, 0.0) if self.decoupled else (0.0, wd)
+            mode = self._adamw_mode(g, c)
             out16 = pf[s:e]
             if p.is_cuda:
-                self._adamw_fn(g)(_lib.dt_code(pf.dtype), p.data_ptr(), g.data_ptr(),
-                                          m.data_ptr(), v.data_ptr(), out16.data_ptr(), e - s,
-                                          float(lr), self.beta1, self.beta2, self.eps,
-                                          float(wd_dec), float(l2), self.gscale.data_ptr(),
-                                          self.found_inf.data_ptr(), self.dev_step.data_ptr(),
-                                          _lib.stream())
+                self._adamw(mode, p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(),
+                            out16.data_ptr(), e - s, float(lr))
             else:
+                _, wd_dec, l2 = mode
                 if int(self.found_inf.item()):
                     continue
                 t = int(self.dev_step.item())

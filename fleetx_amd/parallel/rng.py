@@ -17,6 +17,7 @@ is the exact PyTorch reproduction used by CPU execution and by the kernel
 tests.
 """
 import contextlib
+import weakref
 
 import torch
 
@@ -168,6 +169,23 @@ _TRACKER = RNGStatesTracker()
 
 def get_rng_state_tracker():
     return _TRACKER
+
+
+# Whole-step graph mode: the device int64 the dropout kernels mix into their
+# keys (fx_common.h salt_key), held weakly -- once the engine that owns the
+# tensor is gone, launches read 0 (eager keys), never freed memory.
+_SALT = [None]
+
+
+def set_device_salt(tensor):
+    """Register the step-salt tensor of every later dropout launch (None: off)."""
+    _SALT[0] = None if tensor is None else weakref.ref(tensor)
+
+
+def device_salt_ptr():
+    """Address of the registered salt, 0 without one (read at each launch)."""
+    t = _SALT[0]() if _SALT[0] is not None else None
+    return 0 if t is None else t.data_ptr()
 
 
 def model_parallel_random_seed(seed, mp_rank=0, pp_rank=0, data_rank=0):

@@ -102,9 +102,7 @@ def _fp16_run(graph, overlap, steps=9, inject=(3, 4)):
     """fp16 O2 steps with the scaler growing every 2 good steps; at step
     inject[0] the scale is set to 2^40 (fp16 gradients overflow: skip, and
     with decr_every 1 the scale halves), at inject[1] back to 1024."""
-    from fleetx_amd.ops import _lib
-    _lib.kernels().set_dropout_salt(0)
-    _lib.kernels().set_adamw_lr_ptr(0)
+    from fleetx_amd.parallel import rng
     eng = _engine("float16", extra=(
         "Engine.cuda_graph=%s" % graph, "Engine.mix_precision.incr_every_n_steps=2",
         "Engine.mix_precision.decr_every_n_nan_or_inf=1",
@@ -126,8 +124,7 @@ def _fp16_run(graph, overlap, steps=9, inject=(3, 4)):
     out = {"losses": losses, "scales": scales, "infs": infs,
            "params": eng.buffer.param_flat.detach().clone(), "step": int(opt.dev_step.item()),
            "graph": eng._graph is not None, "gdtype": eng.buffer.grad_dtype}
-    _lib.kernels().set_dropout_salt(0)
-    _lib.kernels().set_adamw_lr_ptr(0)
+    rng.set_device_salt(None)
     return out
 
 

@@ -19,10 +19,9 @@ def _engine(graph, drop, lr=None, steps=8, extra=()):
     from fleetx_amd.models import build_module
     from fleetx_amd.core.engine.eager_engine import EagerEngine
     from fleetx_amd.parallel import topology as topo
-    from fleetx_amd.ops import _lib
+    from fleetx_amd.parallel import rng
     topo.reset_hcg()
-    _lib.kernels().set_dropout_salt(0)
-    _lib.kernels().set_adamw_lr_ptr(0)
+    rng.set_device_salt(None)  # (an earlier engine of the test may still be alive)
     ov = ["Model.hidden_size=256", "Model.num_layers=3", "Model.num_attention_heads=4",
           "Model.vocab_size=1024", "Model.hidden_dropout_prob=%s" % drop,
           "Model.attention_probs_dropout_prob=%s" % drop, "Model.max_position_embeddings=128",
@@ -79,9 +78,8 @@ def test_graph_dropout_masks_change_per_replay():
     assert eng._graph is not None
     assert all(l == l for l in losses)
     assert len(set(round(x, 6) for x in losses[3:])) == 3, losses
-    from fleetx_amd.ops import _lib
-    _lib.kernels().set_dropout_salt(0)
-    _lib.kernels().set_adamw_lr_ptr(0)
+    from fleetx_amd.parallel import rng
+    rng.set_device_salt(None)
 
 
 def test_graph_salt_checkpointed(tmp_path):
@@ -98,9 +96,8 @@ def test_graph_salt_checkpointed(tmp_path):
     eng2.load(ckpt_dir=glob.glob(str(tmp_path / "epoch_0_step_4*"))[0])
     _run(eng2, _batches(1))
     assert int(eng2._graph_salt.item()) == salt + 1
-    from fleetx_amd.ops import _lib
-    _lib.kernels().set_dropout_salt(0)
-    _lib.kernels().set_adamw_lr_ptr(0)
+    from fleetx_amd.parallel import rng
+    rng.set_device_salt(None)
 
 
 def test_graph_short_batch_runs_eagerly():
@@ -115,9 +112,8 @@ def test_graph_short_batch_runs_eagerly():
     l_next = float(eng._fit_impl(bs[0]))
     assert l_short == l_short and l_next == l_next
     assert eng.optimizer.step_count == 5 and int(eng.optimizer.dev_step.item()) == 5
-    from fleetx_amd.ops import _lib
-    _lib.kernels().set_dropout_salt(0)
-    _lib.kernels().set_adamw_lr_ptr(0)
+    from fleetx_amd.parallel import rng
+    rng.set_device_salt(None)
 
 
 def test_graph_with_deferred_overlapped_update_matches_serial(monkeypatch):

@@ -55,14 +55,14 @@ def main():
     ds = torch.ones(1, dtype=torch.int32, device=dev)
     side = torch.cuda.Stream()
 
-    def adamw_once():
+    def adamw_once(grid, wide):
         c = n // a.chunks
         for i in range(a.chunks):
             o = i * c
             ln = n - o if i == a.chunks - 1 else c
-            k.adamw_flat(0, master[o:].data_ptr(), grad[o:].data_ptr(), m1[o:].data_ptr(),
-                         v1[o:].data_ptr(), p16[o:].data_ptr(), ln, 1e-4, 0.9, 0.95, 1e-8, 0.01,
-                         0.0, gs.data_ptr(), fi.data_ptr(), ds.data_ptr(), _lib.stream())
+            k.adamw(0, 0, master[o:].data_ptr(), grad[o:].data_ptr(), m1[o:].data_ptr(),
+                    v1[o:].data_ptr(), p16[o:].data_ptr(), ln, 1e-4, 0.9, 0.95, 1e-8, 0.01, 0.0,
+                    gs.data_ptr(), fi.data_ptr(), ds.data_ptr(), 0, grid, 1, wide, _lib.stream())
 
     shapes = {"qkv": (h, 3 * h), "out": (h, h), "fc1": (h, 4 * h), "fc2": (4 * h, h)}
     only = [s for s in a.only.split(",") if s]
@@ -71,27 +71,25 @@ def main():
         # AdamW alone on a limited number of workgroups: how many CUs the
         # update needs to stream at HBM rate
         for g in [int(x) for x in a.grid_sweep.split(",")]:
-            k.adamw_tune(g, 1, a.wide)
-            adamw_once()
+            adamw_once(g, a.wide)
             torch.cuda.synchronize()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            adamw_once()
+            adamw_once(g, a.wide)
             e1.record()
             torch.cuda.synchronize()
             t = e0.elapsed_time(e1)
             print(json.dumps({"case": "adamw_grid", "grid": g, "wide": a.wide, "ms": round(t, 3),
                               "TB_s": round(30.0 * n / t / 1e9, 2)}), flush=True)
         return
-    # AdamW alone (rate)
+    # AdamW alone (rate); the block shape applies to a capped update only
+    wide = a.wide if a.grid else 0
     with torch.cuda.stream(side):
-        if a.grid:
-            k.adamw_tune(a.grid, 1, a.wide)
-        adamw_once()
+        adamw_once(a.grid, wide)
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(side)
-        adamw_once()
+        adamw_once(a.grid, wide)
         e1.record(side)
     torch.cuda.synchronize()
     t_adam = e0.elapsed_time(e1)
@@ -127,7 +125,7 @@ def main():
             g0, g1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             with torch.cuda.stream(side):
                 s0.record(side)
-                adamw_once()
+                adamw_once(a.grid, wide)
                 s1.record(side)
             g0.record()
             for _ in range(a.iters):

@@ -54,7 +54,7 @@ def main():
     def ln_bwd(ds_in, p):
         k.ln_bwd_row(0, x.data_ptr(), r.data_ptr(), mean.data_ptr(), rstd.data_ptr(), g.data_ptr(),
                      _lib.ptr(ds_in), ds.data_ptr(), (dx if p > 0 else ds).data_ptr(), M, h,
-                     float(p), 7, _lib.stream())
+                     float(p), 7, 0, _lib.stream())
     # the row pass of the two-pass LayerNorm backward (h > 2048): dy, s (+ ds_in)
     # read, ds (+ dropout'd dx) written
     cases += [("ln_bwd_row_dsin_p0.1", lambda: ln_bwd(x, 0.1),

@@ -34,10 +34,11 @@ def main():
     skip = torch.zeros(1, device=dev, dtype=torch.int32)
     step = torch.ones(1, device=dev, dtype=torch.int32)
 
-    def run():
-        k.adamw_flat(0, p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p16.data_ptr(), n,
-                     1e-4, 0.9, 0.95, 1e-8, 0.01, 0.0, gs.data_ptr(), skip.data_ptr(),
-                     step.data_ptr(), _lib.stream())
+    def run(grid, nt, wide):
+        k.adamw(0, 0, p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p16.data_ptr(), n,
+                1e-4, 0.9, 0.95, 1e-8, 0.01, 0.0, gs.data_ptr(), skip.data_ptr(),
+                step.data_ptr(), 0, grid, nt, wide, _lib.stream())
+
     def timeit(fn):
         for _ in range(2):
             fn()
@@ -68,15 +69,13 @@ def main():
         # chip the update takes from the GEMMs beside it
         cases += [(g, 1, w) for w in (0, 1) for g in (32, 48, 64, 96, 128)]
     for grid, nt, wide in cases:
-        k.adamw_tune(grid, nt, wide)
-        ms = timeit(run)
+        ms = timeit(lambda: run(grid, nt, wide))
         tb = 30.0 * n / ms / 1e9
         print(json.dumps({"kernel": "adamw_flat", "grid": grid or "auto", "nontemporal": nt,
                           "block": 1024 if wide else 256, "float4_per_thread": 4 if wide else 2,
                           "n": n, "ms": round(ms, 3), "TB_s": round(tb, 3),
                           "GB_s_per_workgroup": round(1000 * tb / grid, 1) if grid else None,
                           "ms_per_6.65B_params": round(ms * 6.65e9 / n, 2)}))
-    k.adamw_tune(0, 1, 0)
 
 
 if __name__ == "__main__":
