@@ -226,6 +226,17 @@ PYBIND11_MODULE(_kernels, m) {
     return fx_decode_attn(dt, CP(q), CP(kc), CP(vc), P(out), reinterpret_cast<const int*>(lens), B,
                           H, D, maxlen, nsplit, F(ws), sqb, sqh, skb, sks, skh, sob, scale, S(st));
   });
+  m.def("beam_decode_attn", [](int dt, ptr q, ptr kp, ptr vp, ptr plens, ptr kg, ptr vg, ptr glens,
+                               ptr anc, ptr out, ptr ws, int B, int nb, int H, int D, int S, int G,
+                               int nsplit, long sqb, long sqh, long spb, long sps, long sph,
+                               long sgb, long sgs, long sgh, long sab, long sob, float scale,
+                               int nw, ptr st) {
+    return fx_beam_decode_attn(dt, CP(q), CP(kp), CP(vp), reinterpret_cast<const int*>(plens),
+                               CP(kg), CP(vg), reinterpret_cast<const int*>(glens),
+                               reinterpret_cast<const int*>(anc), P(out), F(ws), B, nb, H, D, S, G,
+                               nsplit, sqb, sqh, spb, sps, sph, sgb, sgs, sgh, sab, sob, scale,
+                               nw, S(st));
+  });
   m.def("softmax_fwd", [](int dt, int mdt, ptr x, ptr mask, ptr y, long rows, int Sq, int Sk,
                           long mask_div, float scale, int causal, ptr st) {
     return fx_softmax_fwd(dt, mdt, CP(x), CP(mask), P(y), rows, Sq, Sk, mask_div, scale, causal,

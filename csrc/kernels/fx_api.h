@@ -82,6 +82,10 @@ int fx_sample(int, const void*, long, int, int, float, int, float, const float*,
               float*, hipStream_t);
 int fx_decode_attn(int, const void*, const void*, const void*, void*, const int*, int, int, int,
                    int, int, float*, long, long, long, long, long, long, float, hipStream_t);
+int fx_beam_decode_attn(int, const void*, const void*, const void*, const int*, const void*,
+                        const void*, const int*, const int*, void*, float*, int, int, int, int, int,
+                        int, int, long, long, long, long, long, long, long, long, long, long, float,
+                        int, hipStream_t);
 void fx_embedding_bwd_sorted(int, const int64_t*, const int64_t*, const void*, float*, int, int,
                              long, long, hipStream_t);
 int fx_softmax_fwd(int, int, const void*, const void*, void*, long, int, int, long, float, int,

@@ -225,6 +225,242 @@ __global__ __launch_bounds__(D) void decode_attn_combine_kernel(const float* __r
   out[b * sob + hd * D + d] = Elt<T>::from_f(L > 0.f ? O / L : 0.f);
 }
 
+// Sum over the LPK (8 or 16) consecutive lanes that share a key row, on every
+// lane of the group.  DPP lane permutes (xor 1, xor 2, mirror within 8, mirror
+// within 16): one VALU add each and no LDS-pipeline round trip, which
+// __shfl_xor costs.  With nb beams per key the score reductions are the bulk
+// of the cross-lane traffic of beam_decode_attn_kernel.
+template <int LPK>
+__device__ __forceinline__ float group_sum(float v) {
+  static_assert(LPK == 8 || LPK == 16, "lane group of 8 or 16");
+  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));
+  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false));
+  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, false));
+  if (LPK == 16)
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, false));
+  return v;
+}
+
+// Beam-search decode attention: nb beams per sample share the prompt.
+// q / out: [B*nb, H, D]; prefix caches kp / vp: [B, S, H, D] (spb, sps, sph),
+// plens [B]; generated caches kg / vg: [B*nb, G, H, D] (sgb, sgs, sgh), glens
+// [B] valid slots; anc [B*nb, G] (row stride sab): row b*nb + anc[b*nb+j, s]
+// holds in slot s the key of beam j's ancestor from step s.  anc is trusted to
+// be in [0, nb).
+// The key axis of row b*nb+j is the prefix [0, plens[b]) followed by the
+// glens[b] generated slots; split-K over that axis exactly as above.  One
+// workgroup owns all nb queries of one (b, h, split): a prefix K/V row is
+// loaded once (16-byte loads, U rows in flight per lane group) and scored
+// against every beam, so the prompt is streamed once per sample and not once
+// per beam.  Generated slots are loaded per beam through anc (short; sibling
+// beams that share an ancestor hit the same lines).
+// NB >= nb beams are held in registers (5 and 7 beams run the 6 and 8 beam
+// code with beam 0 repeated and not stored): per lane 8*NB floats of q and of
+// o, so U shrinks as NB grows.  The per-beam blocks of a step are straight-line
+// code (masked keys are selected away, not branched around; the running max
+// starts at a large finite negative so no inf - inf arises): the compiler
+// interleaves the beams' reduce / exp chains, which a wave cannot hide behind
+// other waves at 2 waves per SIMD.  The waves are merged through LDS in rounds
+// of RB beams (static LDS stays far below 64 KB also for 16 waves).
+// Partials go to ws as [(row*H + h)*nsplit + split][D+2]: decode_attn_combine_kernel
+// merges them with its "batch" = B*nb.
+template <typename T, int D, int NB, int NW>
+__global__ __launch_bounds__(64 * NW) void beam_decode_attn_kernel(
+    const uint16_t* __restrict__ q, const uint16_t* __restrict__ kp,
+    const uint16_t* __restrict__ vp, const int* __restrict__ plens,
+    const uint16_t* __restrict__ kg, const uint16_t* __restrict__ vg,
+    const int* __restrict__ glens, const int* __restrict__ anc, float* __restrict__ ws,
+    uint16_t* __restrict__ out, int H, int nb, int nsplit, int chunk, long sqb, long sqh, long spb,
+    long sps, long sph, long sgb, long sgs, long sgh, long sab, long sob, float scale) {
+  constexpr int LPK = D / 8;                     // lanes per key row
+  constexpr int KPW = 64 / LPK;                  // key rows per wave instruction
+  constexpr int U = NB <= 2 ? 4 : NB <= 4 ? 2 : 1;  // prefix rows per lane group per step
+  constexpr int RB = NB * NW <= 32 ? NB : (32 / NW > 0 ? 32 / NW : 1);  // beams per merge round
+  const int split = blockIdx.x % nsplit, bh = blockIdx.x / nsplit;
+  const int b = bh / H, hd = bh % H;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int sub = lane / LPK, c = (lane % LPK) * 8;
+  const int plen = plens[b], len = plen + glens[b];
+  const int k_lo = split * chunk, k_hi = min(len, k_lo + chunk);
+  const int p_hi = min(k_hi, plen);                      // prefix keys [k_lo, p_hi)
+  const int g_lo = max(k_lo, plen) - plen, g_hi = k_hi - plen;  // generated slots [g_lo, g_hi)
+  constexpr float NEG = -1e30f;  // "no key yet": finite, so exp(m - mx) never sees inf - inf
+  const long row0 = (long)b * nb;
+  float qv[NB][8], o[NB][8], m[NB], l[NB];
+#pragma unroll
+  for (int j = 0; j < NB; ++j) {
+    load8<T>(q + (row0 + (j < nb ? j : 0)) * sqb + hd * sqh + c, qv[j]);
+    m[j] = NEG;
+    l[j] = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      qv[j][i] *= scale;
+      o[j][i] = 0.f;
+    }
+  }
+  // ---- prefix: each K/V row is loaded once and scored against all beams
+  const uint16_t* kb = kp + b * spb + hd * sph + c;
+  const uint16_t* vb = vp + b * spb + hd * sph + c;
+  // software pipeline: the rows of step i+1 are requested before step i is
+  // scored, so a wave overlaps its own memory round trip with its math (with
+  // nb beams the math per row is long, and few waves fit per SIMD)
+  constexpr int STEP = NW * KPW * U;
+  uint4 kraw[U], vraw[U], knext[U], vnext[U];
+  if (k_lo < p_hi) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int key = k_lo + (u * NW + w) * KPW + sub;
+      const int kk = key < p_hi ? key : k_lo;  // in-range dummy row
+      kraw[u] = *reinterpret_cast<const uint4*>(kb + (long)kk * sps);
+      vraw[u] = *reinterpret_cast<const uint4*>(vb + (long)kk * sps);
+    }
+  }
+  for (int k0 = k_lo; k0 < p_hi; k0 += STEP) {
+    const bool more = k0 + STEP < p_hi;
+    if (more) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int key = k0 + STEP + (u * NW + w) * KPW + sub;
+        const int kk = key < p_hi ? key : k_lo;
+        knext[u] = *reinterpret_cast<const uint4*>(kb + (long)kk * sps);
+        vnext[u] = *reinterpret_cast<const uint4*>(vb + (long)kk * sps);
+      }
+    }
+    bool ok[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) ok[u] = k0 + (u * NW + w) * KPW + sub < p_hi;
+    float kv[U][8], vv[U][8];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      unpack8<T>(kraw[u], kv[u]);
+      unpack8<T>(vraw[u], vv[u]);
+    }
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+      float sc[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        sc[u] = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) sc[u] += kv[u][i] * qv[j][i];
+      }
+      float mx = m[j];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const float t = group_sum<LPK>(sc[u]);
+        sc[u] = ok[u] ? t : NEG;
+        mx = fmaxf(mx, sc[u]);
+      }
+      const float a = __expf(m[j] - mx);
+      l[j] *= a;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) o[j][i] *= a;
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const float p = ok[u] ? __expf(sc[u] - mx) : 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) o[j][i] += p * vv[u][i];
+        l[j] += p;
+      }
+      m[j] = mx;
+    }
+    if (more) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        kraw[u] = knext[u];
+        vraw[u] = vnext[u];
+      }
+    }
+  }
+  // ---- generated slots: beam j reads slot s from its ancestor's row
+  for (int s0 = g_lo; s0 < g_hi; s0 += NW * KPW) {
+    const int s = s0 + w * KPW + sub;
+    const bool ok = s < g_hi;
+    const int ss = ok ? s : g_lo;  // in-range dummy slot
+    const long soff = (long)ss * sgs + hd * sgh + c;
+    uint4 graw[NB], hraw[NB];
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+      const long row = row0 + anc[(row0 + (j < nb ? j : 0)) * sab + ss];
+      graw[j] = *reinterpret_cast<const uint4*>(kg + row * sgb + soff);
+      hraw[j] = *reinterpret_cast<const uint4*>(vg + row * sgb + soff);
+    }
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+      float kv[8], vv[8];
+      unpack8<T>(graw[j], kv);
+      unpack8<T>(hraw[j], vv);
+      float sc = 0.f;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) sc += kv[i] * qv[j][i];
+      const float t = group_sum<LPK>(sc);
+      sc = ok ? t : NEG;
+      const float mx = fmaxf(m[j], sc);
+      const float a = __expf(m[j] - mx), p = ok ? __expf(sc - mx) : 0.f;
+      l[j] = l[j] * a + p;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) o[j][i] = o[j][i] * a + p * vv[i];
+      m[j] = mx;
+    }
+  }
+  // a state that saw no key is (-inf, 0, 0), as merge_state and the combine pass expect
+#pragma unroll
+  for (int j = 0; j < NB; ++j) m[j] = l[j] > 0.f ? m[j] : -INFINITY;
+  // ---- merge: lane groups of a wave by shuffles, then the waves through LDS
+#pragma unroll
+  for (int j = 0; j < NB; ++j) {
+#pragma unroll
+    for (int off = LPK; off < 64; off <<= 1) {
+      float o2[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) o2[i] = __shfl_xor(o[j][i], off, 64);
+      const float m2 = __shfl_xor(m[j], off, 64), l2 = __shfl_xor(l[j], off, 64);
+      merge_state(m[j], l[j], o[j], m2, l2, o2);
+    }
+  }
+  __shared__ float sm_m[RB][NW * LPK], sm_l[RB][NW * LPK], sm_o[RB][NW * LPK][8];
+#pragma unroll
+  for (int r0 = 0; r0 < NB; r0 += RB) {
+    if (r0 > 0) __syncthreads();
+    if (lane < LPK) {
+#pragma unroll
+      for (int r = 0; r < RB; ++r) {
+        if (r0 + r >= NB) continue;
+        sm_m[r][w * LPK + lane] = m[r0 + r];
+        sm_l[r][w * LPK + lane] = l[r0 + r];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) sm_o[r][w * LPK + lane][i] = o[r0 + r][i];
+      }
+    }
+    __syncthreads();
+    // thread t merges beam r0 + t / LPK, column slice t % LPK
+    const int r = threadIdx.x / LPK, sl = threadIdx.x % LPK, j = r0 + r;
+    if (r < RB && j < nb) {
+      float M = -INFINITY, L = 0.f, O[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) O[i] = 0.f;
+#pragma unroll
+      for (int i = 0; i < NW; ++i)
+        merge_state(M, L, O, sm_m[r][i * LPK + sl], sm_l[r][i * LPK + sl], sm_o[r][i * LPK + sl]);
+      if (nsplit == 1) {  // one split: normalise and store the output directly
+        const float inv = L > 0.f ? 1.f / L : 0.f;
+        float res[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) res[i] = O[i] * inv;
+        store8<T>(out + (row0 + j) * sob + hd * D + sl * 8, res);
+      } else {
+        float* wp = ws + (((row0 + j) * H + hd) * nsplit + split) * (D + 2);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) wp[sl * 8 + i] = O[i];
+        if (sl == 0) {
+          wp[D] = M;
+          wp[D + 1] = L;
+        }
+      }
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" void fx_absmax(int dtype, const void* x, long n, float* out, hipStream_t st) {
@@ -280,5 +516,65 @@ extern "C" int fx_decode_attn(int dt, const void* q, const void* kc, const void*
     return -3;
   }
 #undef FX_DEC
+  return 0;
+}
+
+// Beam decode attention (see beam_decode_attn_kernel).  dt: 0 bf16 / 1 fp16;
+// S / G: allocated prefix rows / generated slots; chunk = keys per split of the
+// S + G key axis; ws: fp32 workspace of B*nb*H*nsplit*(D+2); nw: waves per
+// workgroup, 4 or 8, 0 = by the number of workgroups.
+extern "C" int fx_beam_decode_attn(int dt, const void* q, const void* kp, const void* vp,
+                                   const int* plens, const void* kg, const void* vg,
+                                   const int* glens, const int* anc, void* out, float* ws, int B,
+                                   int nb, int H, int D, int S, int G, int nsplit, long sqb,
+                                   long sqh, long spb, long sps, long sph, long sgb, long sgs,
+                                   long sgh, long sab, long sob, float scale, int nw,
+                                   hipStream_t st) {
+  if (D != 64 && D != 128) return -1;
+  if (nsplit < 1) return -2;
+  if (dt != 0 && dt != 1) return -3;
+  if (nb < 1 || nb > 8) return -4;
+  if (nw != 0 && nw != 4 && nw != 8) return -5;
+  const int chunk = (S + G + nsplit - 1) / nsplit;
+  const int g = B * H * nsplit;
+  // up to one workgroup per CU: 8 waves each (one resident round covers the
+  // CUs with half the partials of 4-wave workgroups); more: 4 waves, of which
+  // 2-3 workgroups fit a CU
+  const bool wide = nw == 8 || (nw == 0 && g <= 256);
+#define FX_BEAM(TT, DD, NBB)                                                                     \
+  do {                                                                                           \
+    if (wide)                                                                                    \
+      beam_decode_attn_kernel<TT, DD, NBB, 8><<<g, 512, 0, st>>>(                                \
+          (const uint16_t*)q, (const uint16_t*)kp, (const uint16_t*)vp, plens,                   \
+          (const uint16_t*)kg, (const uint16_t*)vg, glens, anc, ws, (uint16_t*)out, H, nb,       \
+          nsplit, chunk, sqb, sqh, spb, sps, sph, sgb, sgs, sgh, sab, sob, scale);               \
+    else                                                                                         \
+      beam_decode_attn_kernel<TT, DD, NBB, 4><<<g, 256, 0, st>>>(                                \
+          (const uint16_t*)q, (const uint16_t*)kp, (const uint16_t*)vp, plens,                   \
+          (const uint16_t*)kg, (const uint16_t*)vg, glens, anc, ws, (uint16_t*)out, H, nb,       \
+          nsplit, chunk, sqb, sqh, spb, sps, sph, sgb, sgs, sgh, sab, sob, scale);               \
+  } while (0)
+#define FX_BEAM_NB(TT, DD)                                                                       \
+  do {                                                                                           \
+    switch (nb) {                                                                                \
+      case 1: FX_BEAM(TT, DD, 1); break;                                                         \
+      case 2: FX_BEAM(TT, DD, 2); break;                                                         \
+      case 3: FX_BEAM(TT, DD, 3); break;                                                         \
+      case 4: FX_BEAM(TT, DD, 4); break;                                                         \
+      case 5:                                                                                    \
+      case 6: FX_BEAM(TT, DD, 6); break;                                                         \
+      default: FX_BEAM(TT, DD, 8); break;                                                        \
+    }                                                                                            \
+    if (nsplit > 1)                                                                              \
+      decode_attn_combine_kernel<TT, DD><<<B * nb * H, DD, 0, st>>>(ws, (uint16_t*)out, H,       \
+                                                                    nsplit, sob);                \
+  } while (0)
+  if (dt == 0) {
+    if (D == 128) FX_BEAM_NB(bf16, 128); else FX_BEAM_NB(bf16, 64);
+  } else {
+    if (D == 128) FX_BEAM_NB(f16, 128); else FX_BEAM_NB(f16, 64);
+  }
+#undef FX_BEAM_NB
+#undef FX_BEAM
   return 0;
 }

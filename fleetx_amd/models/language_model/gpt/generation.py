@@ -16,7 +16,10 @@ MI355X design (K18/K19):
   step writes one row per sample in place (no concat / re-allocation as in the
   reference ``_forward_`` path);
 * per-token attention uses the split-free decode kernel
-  (``ops.decode_attention``) that streams the cache once.
+  (``ops.decode_attention``) that streams the cache once;
+* beam search (which the reference accepts and then raises on) keeps the
+  prompt's K/V once per sample and the beams as an ancestor table
+  (``BeamKVCache``, ``ops.beam_decode_attention``): a reorder moves no K/V.
 """
 import os
 import torch
@@ -125,6 +128,25 @@ def top_p_filter(probs, p, min_keep=1):
     return torch.where(mask, torch.zeros_like(probs), probs)
 
 
+def _topk_ties_low(x, k):
+    """Top ``k`` of each row of ``x`` [B, N], highest first, equal values in
+    order of increasing index (``torch.topk`` leaves the order of ties open).
+    Returns (values, indices)."""
+    N = x.shape[1]
+    v1, i1 = torch.topk(x, k, dim=1)
+    kth = v1[:, -1:]
+    # entries above the k-th value are certain; the rest are the lowest indices equal to it
+    rev = N - torch.arange(N, device=x.device)
+    v2, _ = torch.topk(torch.where(x == kth, rev, torch.zeros_like(rev)), k, dim=1)
+    ninf = torch.full_like(v1, float("-inf"))
+    vals = torch.cat([torch.where(v1 > kth, v1, ninf),
+                      torch.where(v2 > 0, kth.expand_as(v1), ninf)], 1)
+    idxs = torch.cat([i1, N - v2], 1)
+    idxs, o = torch.sort(idxs, 1)
+    vals, o = torch.sort(vals.gather(1, o), dim=1, descending=True, stable=True)
+    return vals[:, :k], idxs.gather(1, o)[:, :k]
+
+
 # ----------------------------------------------------------------------------
 # cached decoding
 # ----------------------------------------------------------------------------
@@ -134,6 +156,60 @@ class KVCache:
                   for _ in range(num_layers)]
         self.v = [torch.zeros_like(t) for t in self.k]
         self.max_len = max_len
+
+
+class BeamKVCache:
+    """KV cache for beam search: the prompt once per sample, the generated
+    tokens as a tree.
+
+    * ``k`` / ``v``: per-layer prefix ``[B, S, H, D]`` (``_layer_prefill`` fills
+      it from the B prompts; it is never expanded to ``B*nb`` rows), with
+      ``plens`` int32 ``[B]``;
+    * ``kg`` / ``vg``: per-layer generated ``[B*nb, G, H, D]``; decode step
+      ``t`` appends into slot ``t`` of every row;
+    * ``anc`` int32 ``[B*nb, G]``: ``anc[b*nb+j, s]`` is the sample-local row
+      whose slot ``s`` holds beam ``j``'s ancestor from step ``s``.  A beam
+      reorder only gathers this table (``reorder``); no K/V byte moves.
+    """
+
+    def __init__(self, num_layers, batch, num_beams, prefix_len, gen_len, heads, head_dim, dtype,
+                 device):
+        self.k = [torch.zeros(batch, prefix_len, heads, head_dim, dtype=dtype, device=device)
+                  for _ in range(num_layers)]
+        self.v = [torch.zeros_like(t) for t in self.k]
+        self.kg = [torch.zeros(batch * num_beams, gen_len, heads, head_dim, dtype=dtype,
+                               device=device) for _ in range(num_layers)]
+        self.vg = [torch.zeros_like(t) for t in self.kg]
+        self.anc = torch.zeros(batch * num_beams, gen_len, dtype=torch.int32, device=device)
+        self.plens = torch.zeros(batch, dtype=torch.int32, device=device)
+        self.batch, self.num_beams, self.gen_len = batch, num_beams, gen_len
+        self._self = torch.arange(num_beams, dtype=torch.int32, device=device)
+
+    def reorder(self, parents, t):
+        """Beam ``j`` of sample ``b`` continues beam ``parents[b, j]`` and will
+        write its own K/V into slot ``t``: gather the parents' ancestor rows
+        (through a temporary, so the update never reads its own writes), then
+        point slot ``t`` at the row itself."""
+        B, nb, G = self.batch, self.num_beams, self.gen_len
+        new = self.anc.view(B, nb, G).gather(1, parents[:, :, None].expand(B, nb, G))
+        new[:, :, t] = self._self
+        self.anc.copy_(new.view(B * nb, G))
+
+
+def _gen_kv(cache, li):
+    """The caches a decode step appends to."""
+    if isinstance(cache, BeamKVCache):
+        return cache.kg[li], cache.vg[li]
+    return cache.k[li], cache.v[li]
+
+
+def _attend(cache, li, q, lens_after):
+    """Single-token attention of ``q`` [rows, H, D] against layer ``li``.  For a
+    ``BeamKVCache`` ``lens_after`` is ``glens`` [B], the valid generated slots."""
+    if isinstance(cache, BeamKVCache):
+        return ops.beam_decode_attention(q, cache.k[li], cache.v[li], cache.plens, cache.kg[li],
+                                         cache.vg[li], lens_after, cache.anc)
+    return ops.decode_attention(q, cache.k[li], cache.v[li], lens_after)
 
 
 def _layer_prefill(layer, x, cache, li, lens):
@@ -154,16 +230,19 @@ def _layer_prefill(layer, x, cache, li, lens):
 
 
 def _layer_decode(layer, x, cache, li, pos, lens_after):
-    """One-token pass: x [B, 1, h]; writes K/V at ``pos`` [B] and attends."""
+    """One-token pass: x [B, 1, h]; writes K/V at ``pos`` [B] and attends.  With
+    a ``BeamKVCache`` ``pos`` is the generated slot per row and ``lens_after``
+    the valid slots per sample."""
     attn = layer.attn
     h = layer.ln1(x)
     qkv = attn.qkv_proj(h)
     b = qkv.shape[0]
     qkv5 = qkv.view(b, attn.heads, 3, attn.head_dim)
     ar = torch.arange(b, device=x.device)
-    cache.k[li][ar, pos] = qkv5[:, :, 1]
-    cache.v[li][ar, pos] = qkv5[:, :, 2]
-    o = ops.decode_attention(qkv5[:, :, 0].contiguous(), cache.k[li], cache.v[li], lens_after)
+    kc, vc = _gen_kv(cache, li)
+    kc[ar, pos] = qkv5[:, :, 1]
+    vc[ar, pos] = qkv5[:, :, 2]
+    o = _attend(cache, li, qkv5[:, :, 0].contiguous(), lens_after)
     a, ab = attn.out_proj(o.reshape(b, 1, -1))
     x2, h2 = ops.add_layer_norm(a, ab, x, layer.ln2.weight, layer.ln2.bias, layer.ln2.eps)
     m, mb = layer.mlp(h2)
@@ -195,7 +274,7 @@ def _layer_decode_fused(layer, x, cache, li, pos, lens_after):
     attn, mlp = layer.attn, layer.mlp
     B, h = x.shape[0], x.shape[-1]
     x2d = x.reshape(B, h)
-    kv = (cache.k[li], cache.v[li], pos)
+    kv = _gen_kv(cache, li) + (pos,)
     q = G.decode_linear(x2d, attn.qkv_proj.weight, attn.qkv_proj.bias, G.GV_QKV, qkv_cache=kv,
                         ln=(layer.ln1.weight, layer.ln1.bias, layer.ln1.eps)) if _LN_FUSE else None
     if q is None:
@@ -203,8 +282,7 @@ def _layer_decode_fused(layer, x, cache, li, pos, lens_after):
                             qkv_cache=kv)
     if q is None:
         return None
-    o = ops.decode_attention(q.view(B, attn.heads, attn.head_dim), cache.k[li], cache.v[li],
-                             lens_after)
+    o = _attend(cache, li, q.view(B, attn.heads, attn.head_dim), lens_after)
     x2 = G.decode_linear(o.view(B, -1), attn.out_proj.weight, attn.out_proj.bias, G.GV_RES,
                          res=x2d)
     f = G.decode_linear(x2, mlp.fc1.weight, mlp.fc1.bias, G.GV_GELU,
@@ -244,14 +322,30 @@ class _GraphedDecodeStep:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):  # warm-up off the capture stream
-                out = self.gen._decode_step(self.nxt, self.cur, self.cache)
+                out = self._run()
             torch.cuda.current_stream().wait_stream(side)
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):
-                self.logits = self.gen._decode_step(self.nxt, self.cur, self.cache)
+                self.logits = self._run()
             return out
         self.graph.replay()
         return self.logits
+
+    def _run(self):
+        return self.gen._decode_step(self.nxt, self.cur, self.cache)
+
+
+class _GraphedBeamStep(_GraphedDecodeStep):
+    """The beam decode step under the same capture-once / replay scheme.  Beyond
+    tokens and positions, the slot, ``glens`` and the cache's ``anc`` table are
+    static device tensors that the loop updates in place between replays."""
+
+    def __init__(self, gen, cache, slot, glens):
+        super().__init__(gen, cache, cache.batch * cache.num_beams)
+        self.slot, self.glens = slot, glens
+
+    def _run(self):
+        return self.gen._beam_decode_step(self.nxt, self.cur, self.cache, self.slot, self.glens)
 
 
 class GPTForGeneration(torch.nn.Module):
@@ -279,8 +373,18 @@ class GPTForGeneration(torch.nn.Module):
         self.use_hip_graph = bool(c.get("use_hip_graph", True))
         # decode layers as five fused kernels with weight-streaming GEMVs (K19)
         self.fused_decode = bool(c.get("fused_decode", True))
-        if self.decode_strategy not in ("sampling", "greedy_search"):
-            raise ValueError("decode_strategy must be sampling or greedy_search")
+        self.length_penalty = c.get("length_penalty", 0.0)
+        self.early_stopping = bool(c.get("early_stopping", False))
+        if self.decode_strategy not in ("sampling", "greedy_search", "beam_search"):
+            raise ValueError("decode_strategy must be sampling, greedy_search or beam_search")
+        if self.decode_strategy == "beam_search":
+            if self.num_beam_groups > 1:
+                raise ValueError("diverse beam search (num_beam_groups > 1) is not supported yet")
+            if self.num_beams < 1:
+                raise ValueError("num_beams must be at least 1")
+            if self.num_return_sequences > self.num_beams:
+                raise ValueError("num_return_sequences (%d) must not exceed num_beams (%d)"
+                                 % (self.num_return_sequences, self.num_beams))
 
     def _processors(self, max_len):
         procs = LogitsProcessorList()
@@ -300,15 +404,25 @@ class GPTForGeneration(torch.nn.Module):
     def _decode_step(self, nxt, cur, cache):
         """Embed token ``nxt`` at position ``cur`` [B], run every layer against
         the KV cache (appending this token), return fp32 logits [B, V]."""
+        return self._step(nxt, cur, cache, cur, (cur + 1).to(torch.int32))
+
+    def _beam_decode_step(self, nxt, pos, cache, slot, glens):
+        """Beam decode step on a ``BeamKVCache``: embed token ``nxt`` [B*nb] at
+        position ``pos`` [B*nb], append K/V into ``slot`` [B*nb] (the step
+        number, the same for every row) of the generated caches, attend over
+        the shared prefix and, through ``cache.anc``, ``glens`` [B] generated
+        slots; return fp32 logits [B*nb, V]."""
+        return self._step(nxt, pos, cache, slot, glens)
+
+    def _step(self, nxt, pos, cache, wpos, after):
         x = ops.embedding(nxt[:, None], self.gpt.embeddings.word_embeddings.weight,
-                          cur[:, None], self.gpt.embeddings.position_embeddings, 0) \
-            if topo.mp_world_size() == 1 else self.gpt.embeddings(nxt[:, None], cur[:, None])
-        after = (cur + 1).to(torch.int32)
+                          pos[:, None], self.gpt.embeddings.position_embeddings, 0) \
+            if topo.mp_world_size() == 1 else self.gpt.embeddings(nxt[:, None], pos[:, None])
         fused = self.fused_decode and x.is_cuda and x.shape[0] <= 16
         for li, layer in enumerate(self.gpt.layers):
-            y = _layer_decode_fused(layer, x, cache, li, cur, after) \
+            y = _layer_decode_fused(layer, x, cache, li, wpos, after) \
                 if fused and _fusable(layer) else None
-            x = y if y is not None else _layer_decode(layer, x, cache, li, cur, after)
+            x = y if y is not None else _layer_decode(layer, x, cache, li, wpos, after)
         x = self.gpt.final_ln(x)
         return self._logits(x[:, 0])
 
@@ -327,8 +441,11 @@ class GPTForGeneration(torch.nn.Module):
     @torch.no_grad()
     def generate(self, input_ids, lens=None, max_length=None, seed=None):
         """input_ids: [B, S] right-padded; lens: [B] prompt lengths.
-        Returns (generated ids [B, T], scores [B])."""
+        Returns (generated ids [B, T], scores [B]); with ``decode_strategy:
+        beam_search`` see ``_beam_search``."""
         self.eval()
+        if self.decode_strategy == "beam_search":
+            return self._beam_search(input_ids, lens, max_length)
         dev = input_ids.device
         if self.num_return_sequences > 1:
             input_ids = input_ids.repeat_interleave(self.num_return_sequences, 0)
@@ -408,6 +525,150 @@ class GPTForGeneration(torch.nn.Module):
         if not out_tokens:
             return torch.zeros(B, 0, dtype=torch.long, device=dev), scores
         return torch.stack(out_tokens, 1), scores
+
+    def _beam_search(self, input_ids, lens=None, max_length=None):
+        """Beam search with ``nb = num_beams`` beams per sample on a
+        ``BeamKVCache``.  Returns ``ids [B*num_return_sequences, T]``, best
+        first per sample and padded with ``pad``, and the normalised
+        ``scores [B*num_return_sequences]``.
+
+        Semantics (the brute-force oracle of tests/test_beam_search_cpu.py
+        implements exactly this):
+
+        * the processors (min length, repetition penalty, forced BOS / EOS) act
+          on the fp32 logits as in the sampling path, then ``log_softmax``;
+          temperature, ``top_k`` and ``top_p`` are ignored;
+        * step 0 selects from the single prefill row per sample; later steps
+          from ``cand = beam_score[:, None] + logp`` over ``nb*V`` per sample;
+        * the top ``2*nb`` candidates are walked highest first, ties towards
+          the lower flat ``(beam, token)`` index.  An EOS candidate with rank
+          ``< nb`` becomes a finished hypothesis with score
+          ``cand / n**length_penalty`` (``n`` = generated tokens including the
+          EOS), an EOS candidate with rank ``>= nb`` is dropped, any other
+          candidate becomes a running beam until ``nb`` are kept;
+        * the pool keeps the best ``nb`` hypotheses per sample (on equal
+          scores the earlier one).  A sample is done when its pool is full and
+          either ``early_stopping`` is set or the best running beam, normalised
+          at the current length, does not beat the pool's worst.  A done sample
+          adds nothing more to its pool;
+        * at ``max_dec_len``, or at the position limit, the running beams of
+          the samples that are not done enter the pool the same way.
+
+        The prefill runs on the B prompts only.  Decode step ``t`` embeds the
+        ``B*nb`` chosen tokens at position ``lens[b] + t`` and appends K/V into
+        slot ``t``; a reorder gathers ``cache.anc`` and the token history, no
+        K/V moves.  Selection and the pool stay in torch, with one host
+        synchronisation per step (the termination check, only with an EOS)."""
+        dev = input_ids.device
+        B, S = input_ids.shape
+        nb, nret = self.num_beams, self.num_return_sequences
+        lens = lens.to(dev) if lens is not None else torch.full((B,), S, device=dev,
+                                                                dtype=torch.long)
+        max_new = max_length or self.max_length
+        cfg = self.gpt.cfg
+        # selection steps, as in the sampling loop: positions stay below the limit
+        N = max(0, min(max_new, cfg.max_position_embeddings - int(lens.max().item())))
+        if N == 0:
+            return (torch.zeros(B * nret, 0, dtype=torch.long, device=dev),
+                    torch.zeros(B * nret, device=dev))
+        p = next(self.parameters())
+        attn0 = self.gpt.layers[0].attn
+        G = max(N - 1, 1)
+        cache = BeamKVCache(len(self.gpt.layers), B, nb, S, G, attn0.heads, attn0.head_dim,
+                            p.dtype, dev)
+        cache.plens.copy_(lens)
+        # ---- prefill on the B prompts
+        pos = torch.arange(S, device=dev).unsqueeze(0).expand(B, S)
+        x = self.gpt.embeddings(input_ids, pos)
+        for li, layer in enumerate(self.gpt.layers):
+            x = _layer_prefill(layer, x, cache, li, cache.plens)
+        x = self.gpt.final_ln(x)
+        logits = self._logits(x[torch.arange(B, device=dev), lens - 1])
+        V = logits.shape[-1]
+        procs = self._processors(max_new)
+        eos = self.eos_token_id
+        pad = self.pad_token_id if self.pad_token_id is not None else (eos if eos is not None else 0)
+        lp = float(self.length_penalty)
+        ninf = float("-inf")
+        beam_score = torch.zeros(B, 1, device=dev)
+        hist = torch.full((B, nb, N), pad, dtype=torch.long, device=dev)   # generated tokens
+        history = input_ids                                                  # prompt + generated
+        pool_score = torch.full((B, nb), ninf, device=dev)
+        pool_tok = torch.full((B, nb, N), pad, dtype=torch.long, device=dev)
+        done = torch.zeros(B, dtype=torch.bool, device=dev)
+        slot = torch.zeros(B * nb, dtype=torch.long, device=dev)
+        glens = torch.zeros(B, dtype=torch.int32, device=dev)
+        rpos = lens.repeat_interleave(nb)
+        graphed = None
+
+        def pool_add(score, toks):
+            # score [B, nb] (-inf: no entry), toks [B, nb, N]; earlier entries win ties
+            both = torch.cat([pool_score, score], 1)
+            top, order = torch.sort(both, dim=1, descending=True, stable=True)
+            both_tok = torch.cat([pool_tok, toks], 1)
+            return top[:, :nb], both_tok.gather(1, order[:, :nb, None].expand(B, nb, N))
+
+        for t in range(N):
+            for pr in procs:
+                if hasattr(pr, "cur_len"):
+                    pr.cur_len = t
+            logp = torch.log_softmax(procs(history, logits), -1)
+            nrow = logp.shape[0] // B                                        # 1 at step 0
+            cand = (beam_score.view(B, nrow, 1) + logp.view(B, nrow, V)).view(B, nrow * V)
+            val, flat = _topk_ties_low(cand, 2 * nb)
+            parent, tok = flat // V, flat % V
+            is_eos = tok == eos if eos is not None else torch.zeros_like(tok, dtype=torch.bool)
+            # running beams: the first nb candidates that are not EOS, in order
+            keep = torch.sort(is_eos.to(torch.int8), dim=1, stable=True).indices[:, :nb]
+            beam_score = val.gather(1, keep)
+            parent_k, tok_k = parent.gather(1, keep), tok.gather(1, keep)
+            prev = hist if nrow == nb else hist[:, :1]
+            if eos is not None:
+                # finished hypotheses: EOS candidates of rank < nb (not for done samples)
+                fin = is_eos[:, :nb] & ~done[:, None]
+                fscore = torch.where(fin, val[:, :nb] / float(t + 1) ** lp,
+                                     torch.full_like(val[:, :nb], ninf))
+                ftok = prev.gather(1, parent[:, :nb, None].expand(B, nb, N))
+                ftok[:, :, t] = tok[:, :nb]
+                pool_score, pool_tok = pool_add(fscore, ftok)
+            hist = prev.gather(1, parent_k[:, :, None].expand(B, nb, N))
+            hist[:, :, t] = tok_k
+            if eos is not None:
+                full = pool_score[:, -1] > ninf
+                best = beam_score[:, 0] / float(t + 1) ** lp
+                done = done | (full & (pool_score[:, -1] >= best)) if not self.early_stopping \
+                    else done | full
+                if bool(done.all()):
+                    break
+            if t == N - 1:
+                break
+            # ---- reorder (ancestor table only) and one decode step into slot t
+            if nrow == nb:
+                cache.reorder(parent_k, t)
+            else:
+                cache.anc[:, t] = cache._self.repeat(B)
+            history = torch.cat([input_ids.repeat_interleave(nb, 0),
+                                 hist.view(B * nb, N)[:, :t + 1]], 1)
+            slot.fill_(t)
+            glens.fill_(t + 1)
+            nxt, cur = tok_k.reshape(B * nb), rpos + t
+            if graphed is None and self.use_hip_graph and dev.type == "cuda" \
+                    and topo.mp_world_size() == 1:
+                graphed = _GraphedBeamStep(self, cache, slot, glens)
+            logits = graphed(nxt, cur) if graphed is not None else \
+                self._beam_decode_step(nxt, cur, cache, slot, glens)
+        # ---- the running beams of the samples that are not done enter the pool
+        n = t + 1
+        fscore = torch.where(done[:, None], torch.full_like(beam_score, ninf),
+                             beam_score / float(n) ** lp)
+        pool_score, pool_tok = pool_add(fscore, hist)
+        ids, scores = pool_tok[:, :nret], pool_score[:, :nret]
+        if eos is not None:
+            # trim to the longest returned hypothesis (a finished one ends at its EOS)
+            has = ids[:, :, :n] == eos
+            n = int(torch.where(has.any(-1), has.int().argmax(-1) + 1,
+                                torch.full_like(ids[:, :, 0], n)).max().item())
+        return ids[:, :, :n].reshape(B * nret, n), scores.reshape(B * nret)
 
     def forward(self, input_ids, lens=None):
         return self.generate(input_ids, lens)

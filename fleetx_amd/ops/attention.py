@@ -283,3 +283,100 @@ def decode_attention(q, k_cache, v_cache, lens, scale=None, nsplit=None):
     if rc != 0:
         raise NotImplementedError("decode attention supports head_dim 64/128 (rc %d)" % rc)
     return out
+
+
+BEAM_KERNEL_MAX = 8  # beams per sample the kernel keeps in registers
+
+
+def beam_decode_splits(B, H, maxlen, target_wgs=256, min_chunk=192):
+    """Split-K factor for beam decode attention.  A workgroup covers all beams
+    of one (sample, head) and runs 8 waves at 2-3 waves per SIMD, so one
+    workgroup per CU is one full round: at most ``target_wgs`` workgroups
+    (measured, H 32, D 128, prompts 1024 / 4096: 256 workgroups beat both 128
+    and 384 at 4 and 8 beams; every further split also lengthens the serial
+    combine pass), at least ``min_chunk`` keys per split."""
+    n = max(1, target_wgs // max(1, B * H))
+    return max(1, min(n, -(-maxlen // min_chunk)))
+
+
+def _beam_attention_formula(q, kp, vp, plens, kg, vg, glens, anc, scale):
+    """fp32 math built from gathers (CPU path, unsupported shapes, test oracle)."""
+    R, H, D = q.shape
+    B, S = kp.shape[0], kp.shape[1]
+    G = kg.shape[1]
+    nb = R // B
+    dev = q.device
+    base = (torch.arange(R, device=dev) // nb * nb).view(R, 1)
+    # [R, G]; slots at or beyond glens may hold anything
+    rows = base + anc.to(dev).long().clamp(0, nb - 1)
+    slots = torch.arange(G, device=dev).view(1, G).expand(R, G)
+    kgen, vgen = kg[rows, slots].float(), vg[rows, slots].float()      # [R, G, H, D]
+    qf = q.float()
+    sp = torch.einsum("rhd,rshd->rhs", qf, kp.float().repeat_interleave(nb, 0)) * scale
+    sg = torch.einsum("rhd,rghd->rhg", qf, kgen) * scale
+    pl = plens.to(dev).long().repeat_interleave(nb).view(R, 1, 1)
+    gl = glens.to(dev).long().repeat_interleave(nb).view(R, 1, 1)
+    mp = torch.arange(S, device=dev).view(1, 1, S) >= pl
+    mg = torch.arange(G, device=dev).view(1, 1, G) >= gl
+    s = torch.cat([sp.masked_fill(mp, float("-inf")), sg.masked_fill(mg, float("-inf"))], -1)
+    p = torch.nan_to_num(torch.softmax(s, -1), nan=0.0)
+    # masked keys may hold anything (NaN included): 0 * NaN must not reach the sum
+    vpre = torch.where(mp.view(R, S, 1, 1), 0.0, vp.float().repeat_interleave(nb, 0))
+    vgen = torch.where(mg.view(R, G, 1, 1), 0.0, vgen)
+    o = torch.einsum("rhs,rshd->rhd", p[..., :S], vpre) \
+        + torch.einsum("rhg,rghd->rhd", p[..., S:], vgen)
+    return o.to(q.dtype)
+
+
+def beam_decode_attention(q, kp, vp, plens, kg, vg, glens, anc, scale=None, nsplit=None,
+                          waves=0):
+    """Single-token attention for ``nb`` beams per sample over a shared prompt
+    and an ancestor-indexed tree of generated tokens (split-K, bf16 / fp16).
+
+    q: [B*nb, H, D]; prefix caches kp / vp: [B, S, H, D], stored once per
+    sample, with plens int32 [B]; generated caches kg / vg: [B*nb, G, H, D]
+    with glens int32 [B] valid slots (the token being decoded included);
+    anc int32 [B*nb, G]: ``anc[b*nb+j, s]`` is the sample-local index of the
+    row whose slot ``s`` holds beam ``j``'s ancestor from step ``s``.  Row
+    ``b*nb+j`` attends to ``kp[b, :plens[b]]`` and to
+    ``kg[b*nb + anc[b*nb+j, s], s]`` for ``s < glens[b]``; values likewise.
+
+    The kernel (1 <= nb <= 8, head_dim 64 / 128, GPU tensors) loads each prefix
+    row once for all beams.  It trusts ``anc`` to lie in ``[0, nb)`` and the
+    lengths to lie within the caches: neither is checked.  Anything else runs
+    the fp32 gather formula.  ``waves``: waves per workgroup, 4 or 8 (0: chosen
+    by the number of workgroups).
+    """
+    R, H, D = q.shape
+    B, S = kp.shape[0], kp.shape[1]
+    G = kg.shape[1]
+    if R % B or kg.shape[0] != R or anc.shape != (R, G):
+        raise ValueError("beam decode attention: q / kg / anc rows must be B*nb, anc [B*nb, G]")
+    nb = R // B
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    if not q.is_cuda or nb > BEAM_KERNEL_MAX or D not in (64, 128):
+        return _beam_attention_formula(q, kp, vp, plens, kg, vg, glens, anc, scale)
+    dt = _lib.dt_code(q.dtype)
+    for t in (kp, vp, kg, vg):
+        if t.dtype != q.dtype:
+            raise TypeError("beam decode attention: q / cache dtypes differ")
+    if kp.stride() != vp.stride() or kg.stride() != vg.stride() or kp.stride(-1) != 1 \
+            or kg.stride(-1) != 1 or q.stride(-1) != 1:
+        raise ValueError("beam decode attention: K and V caches must share a layout with "
+                         "contiguous head dim")
+    anc = anc.to(torch.int32)
+    if anc.stride(-1) != 1:
+        anc = anc.contiguous()
+    ns = nsplit or beam_decode_splits(B, H, S + G)
+    out = torch.empty(R, H, D, device=q.device, dtype=q.dtype)
+    ws = torch.empty(R * H * ns * (D + 2), device=q.device, dtype=torch.float32)
+    rc = _lib.kernels().beam_decode_attn(
+        dt, q.data_ptr(), kp.data_ptr(), vp.data_ptr(),
+        plens.to(torch.int32).contiguous().data_ptr(),
+        kg.data_ptr(), vg.data_ptr(), glens.to(torch.int32).contiguous().data_ptr(), anc.data_ptr(),
+        out.data_ptr(), ws.data_ptr(), B, nb, H, D, S, G, ns, q.stride(0), q.stride(1),
+        kp.stride(0), kp.stride(1), kp.stride(2), kg.stride(0), kg.stride(1), kg.stride(2),
+        anc.stride(0), out.stride(0), float(scale), int(waves), _lib.stream())
+    if rc != 0:
+        raise NotImplementedError("beam decode attention: unsupported shape (rc %d)" % rc)
+    return out

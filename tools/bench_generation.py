@@ -3,6 +3,7 @@ without the fused decode layer (K19: weight-streaming GEMVs with sub-layer
 epilogues).  Random-init weights, bf16.
 
     python tools/bench_generation.py [--model gpt3-1.3B] [--batch 1 8 16] [--tokens 64]
+                                     [--strategy beam_search --num-beams 4]
 
 One JSON line per (batch, fused): ms/token, tokens/s and the effective weight
 stream rate (parameter bytes / ms per token)."""
@@ -26,6 +27,9 @@ def main():
     ap.add_argument("--prompt", type=int, default=128)
     ap.add_argument("--tokens", type=int, default=64)
     ap.add_argument("--fused-only", action="store_true")
+    ap.add_argument("--strategy", default="greedy_search",
+                    choices=["greedy_search", "sampling", "beam_search"])
+    ap.add_argument("--num-beams", type=int, default=1)
     args = ap.parse_args()
     from fleetx_amd.models.language_model.gpt.model import GPTConfig, GPTForPretraining
     from fleetx_amd.models.language_model.gpt.generation import GPTForGeneration
@@ -39,7 +43,8 @@ def main():
         prompt = torch.randint(0, 50304, (B, args.prompt), device="cuda")
         for fused in ((True,) if args.fused_only else (False, True)):
             gen = GPTForGeneration(model, {"max_dec_len": args.tokens, "fused_decode": fused,
-                                           "decode_strategy": "greedy_search"})
+                                           "decode_strategy": args.strategy,
+                                           "num_beams": args.num_beams})
             gen.generate(prompt, max_length=8)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -53,7 +58,9 @@ def main():
             ms = 1e3 * (t - t_pre) / max(1, ids.shape[1] - 1)
             persistent = fused and B <= 4 and \
                 os.environ.get("FLEETX_DECODE_PERSISTENT", "0") == "1"
-            print(json.dumps({"model": args.model, "batch": B, "fused_decode": fused,
+            print(json.dumps({"model": args.model, "batch": B, "strategy": args.strategy,
+                              "num_beams": args.num_beams if args.strategy == "beam_search" else 1,
+                              "fused_decode": fused,
                               "persistent_layers": persistent,
                               "ms_per_token": round(ms, 3),
                               "tokens_per_s": round(B * 1e3 / ms, 1),
