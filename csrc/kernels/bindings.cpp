@@ -276,6 +276,16 @@ PYBIND11_MODULE(_kernels, m) {
                           ldy, P(kc), P(vc), reinterpret_cast<const long*>(pos), heads, head_dim,
                           maxlen, CP(ln_w), CP(ln_b), ln_eps, S(st));
   });
+  // the same with int8 weights and one fp32 scale per output row (decode_gemv_w8.hip)
+  m.def("decode_gemv_w8", [](int dt, int epi, int M, int N, int K, ptr x, long ldx, ptr wq, long ldw,
+                             ptr wscale, ptr bias, ptr res, long ldres, ptr y, long ldy, ptr kc,
+                             ptr vc, ptr pos, int heads, int head_dim, int maxlen, ptr ln_w,
+                             ptr ln_b, float ln_eps, ptr st) {
+    return fx_decode_gemv_w8(dt, epi, M, N, K, CP(x), ldx, reinterpret_cast<const int8_t*>(wq), ldw,
+                             reinterpret_cast<const float*>(wscale), CP(bias), CP(res), ldres,
+                             P(y), ldy, P(kc), P(vc), reinterpret_cast<const long*>(pos), heads,
+                             head_dim, maxlen, CP(ln_w), CP(ln_b), ln_eps, S(st));
+  });
   // CU-masked stream (streams.hip): returns (stream handle, CUs selected)
   m.def("cumask_stream_create", [](int ncu) {
     int got = 0;

@@ -104,6 +104,9 @@ void fx_gemm_set_xrect(int);
 int fx_decode_gemv(int, int, int, int, int, const void*, long, const void*, long, const void*,
                    const void*, long, void*, long, void*, void*, const long*, int, int, int,
                    const void*, const void*, float, hipStream_t);
+int fx_decode_gemv_w8(int, int, int, int, int, const void*, long, const int8_t*, long, const float*,
+                      const void*, const void*, long, void*, long, void*, void*, const long*, int,
+                      int, int, const void*, const void*, float, hipStream_t);
 hipStream_t fx_cumask_stream_create(int, int*);
 int fx_stream_destroy(hipStream_t);
 int fx_comm_max_world();

@@ -22,6 +22,8 @@ MI355X design (K18/K19):
   (``BeamKVCache``, ``ops.beam_decode_attention``): a reorder moves no K/V.
 """
 import os
+import warnings
+
 import torch
 import torch.nn.functional as F
 
@@ -261,7 +263,17 @@ def _fusable(layer):
 _LN_FUSE = os.environ.get("FLEETX_DECODE_LN_FUSE", "1") == "1"
 
 
-def _layer_decode_fused(layer, x, cache, li, pos, lens_after):
+def _dlin(G, x, lin, epi, q8, **kw):
+    """One decode GEMV of ``lin``: on its int8 copy ``q8 = (q, scale)`` where
+    there is one and the int8 kernel covers the call, else on the 16-bit weight."""
+    if q8 is not None:
+        y = G.decode_linear_w8(x, q8[0], q8[1], lin.bias, epi, **kw)
+        if y is not None:
+            return y
+    return G.decode_linear(x, lin.weight, lin.bias, epi, **kw)
+
+
+def _layer_decode_fused(layer, x, cache, li, pos, lens_after, w8=None):
     """One-token pass as four GEMV launches and the attention (K19, the
     fused_multi_transformer counterpart): [LN1 + QKV GEMV + bias, K/V appended
     to the cache in the epilogue] -> split-K decode attention -> [out-proj
@@ -269,27 +281,27 @@ def _layer_decode_fused(layer, x, cache, li, pos, lens_after):
     bias + residual].  The LayerNorms run as GEMV prologues (each block
     normalises the few rows into LDS); shapes the fused prologue does not
     cover fall back to a separate LayerNorm launch.  Returns None when a GEMV
-    does not cover the shape (batch > 16)."""
+    does not cover the shape (batch > 16).  ``w8`` (``weight_quant: int8``) maps
+    ``qkv_proj`` / ``out_proj`` / ``fc1`` / ``fc2`` to this layer's int8 copies."""
     from ....ops import gemm as G
     attn, mlp = layer.attn, layer.mlp
+    w8 = w8 or {}
     B, h = x.shape[0], x.shape[-1]
     x2d = x.reshape(B, h)
     kv = _gen_kv(cache, li) + (pos,)
-    q = G.decode_linear(x2d, attn.qkv_proj.weight, attn.qkv_proj.bias, G.GV_QKV, qkv_cache=kv,
-                        ln=(layer.ln1.weight, layer.ln1.bias, layer.ln1.eps)) if _LN_FUSE else None
+    q = _dlin(G, x2d, attn.qkv_proj, G.GV_QKV, w8.get("qkv_proj"), qkv_cache=kv,
+              ln=(layer.ln1.weight, layer.ln1.bias, layer.ln1.eps)) if _LN_FUSE else None
     if q is None:
-        q = G.decode_linear(layer.ln1(x2d), attn.qkv_proj.weight, attn.qkv_proj.bias, G.GV_QKV,
-                            qkv_cache=kv)
+        q = _dlin(G, layer.ln1(x2d), attn.qkv_proj, G.GV_QKV, w8.get("qkv_proj"), qkv_cache=kv)
     if q is None:
         return None
     o = _attend(cache, li, q.view(B, attn.heads, attn.head_dim), lens_after)
-    x2 = G.decode_linear(o.view(B, -1), attn.out_proj.weight, attn.out_proj.bias, G.GV_RES,
-                         res=x2d)
-    f = G.decode_linear(x2, mlp.fc1.weight, mlp.fc1.bias, G.GV_GELU,
-                        ln=(layer.ln2.weight, layer.ln2.bias, layer.ln2.eps)) if _LN_FUSE else None
+    x2 = _dlin(G, o.view(B, -1), attn.out_proj, G.GV_RES, w8.get("out_proj"), res=x2d)
+    f = _dlin(G, x2, mlp.fc1, G.GV_GELU, w8.get("fc1"),
+              ln=(layer.ln2.weight, layer.ln2.bias, layer.ln2.eps)) if _LN_FUSE else None
     if f is None:
-        f = G.decode_linear(layer.ln2(x2), mlp.fc1.weight, mlp.fc1.bias, G.GV_GELU)
-    out = G.decode_linear(f, mlp.fc2.weight, mlp.fc2.bias, G.GV_RES, res=x2)
+        f = _dlin(G, layer.ln2(x2), mlp.fc1, G.GV_GELU, w8.get("fc1"))
+    out = _dlin(G, f, mlp.fc2, G.GV_RES, w8.get("fc2"), res=x2)
     return out.view(B, 1, h)
 
 
@@ -375,6 +387,13 @@ class GPTForGeneration(torch.nn.Module):
         self.fused_decode = bool(c.get("fused_decode", True))
         self.length_penalty = c.get("length_penalty", 0.0)
         self.early_stopping = bool(c.get("early_stopping", False))
+        # weight-only int8 copies of the decode GEMV weights (None: 16-bit weights)
+        self.weight_quant = c.get("weight_quant")
+        if self.weight_quant not in (None, "int8"):
+            raise ValueError("weight_quant must be None or 'int8' (got %r)" % (self.weight_quant,))
+        self._w8 = None        # {"layers": [{name: (q, scale)}], "head": (q, scale)}
+        self._w8_src = []      # (weight, _version, data_ptr) of every quantised weight
+        self._w8_warned = False
         if self.decode_strategy not in ("sampling", "greedy_search", "beam_search"):
             raise ValueError("decode_strategy must be sampling, greedy_search or beam_search")
         if self.decode_strategy == "beam_search":
@@ -401,6 +420,62 @@ class GPTForGeneration(torch.nn.Module):
             procs.append(ForcedEOSTokenLogitsProcessor(max_len, self.forced_eos_token_id))
         return procs
 
+    # ---- weight-only int8 decode (weight_quant: int8)
+    def _w8_sources(self):
+        """The weights the decode step streams: four per fusable layer and the
+        tied embedding table (as the LM head)."""
+        per_layer = []
+        for layer in self.gpt.layers:
+            per_layer.append({"qkv_proj": layer.attn.qkv_proj.weight,
+                              "out_proj": layer.attn.out_proj.weight,
+                              "fc1": layer.mlp.fc1.weight, "fc2": layer.mlp.fc2.weight}
+                             if _fusable(layer) else {})
+        return per_layer, self.gpt.embeddings.word_embeddings.weight
+
+    def requantize(self):
+        """(Re)build the int8 copies from the current 16-bit weights.  The
+        16-bit weights stay resident (prefill and the embedding lookup use
+        them): the int8 path buys decode bandwidth, not memory.  Returns True
+        when the int8 path is active; on CPU or under tensor parallel the key
+        is accepted and ignored with one warning (those paths do not stream
+        weights through the decode GEMV)."""
+        if self.weight_quant is None:
+            return False
+        head = self.gpt.embeddings.word_embeddings.weight
+        if not head.is_cuda or topo.mp_world_size() != 1 or not self.fused_decode:
+            if not self._w8_warned:
+                warnings.warn("weight_quant=%r is ignored: the int8 decode path needs a GPU, "
+                              "fused_decode and no tensor parallelism" % (self.weight_quant,))
+                self._w8_warned = True
+            self._w8, self._w8_src = None, []
+            return False
+        per_layer, head = self._w8_sources()
+        src = []
+
+        def quant(w):
+            src.append((w, w._version, w.data_ptr()))
+            return ops.quantize_weight_int8(w)
+        with torch.no_grad():
+            self._w8 = {"layers": [{k: quant(w) for k, w in d.items()} for d in per_layer],
+                        "head": quant(head)}
+        self._w8_src = src
+        return True
+
+    def _w8_refresh(self):
+        """At the start of ``generate()``: quantise on first use and whenever a
+        source weight was written in place or replaced since."""
+        if self.weight_quant is None or self._w8_warned:
+            return
+        stale = self._w8 is None
+        if not stale:
+            cur = [w for d in self._w8_sources()[0] for w in d.values()]
+            cur.append(self.gpt.embeddings.word_embeddings.weight)
+            stale = len(cur) != len(self._w8_src) or any(
+                w is not s or w._version != v or w.data_ptr() != p
+                for w, (s, v, p) in zip(cur, self._w8_src))
+        if stale:
+            self.requantize()
+
     def _decode_step(self, nxt, cur, cache):
         """Embed token ``nxt`` at position ``cur`` [B], run every layer against
         the KV cache (appending this token), return fp32 logits [B, V]."""
@@ -419,19 +494,28 @@ class GPTForGeneration(torch.nn.Module):
                           pos[:, None], self.gpt.embeddings.position_embeddings, 0) \
             if topo.mp_world_size() == 1 else self.gpt.embeddings(nxt[:, None], pos[:, None])
         fused = self.fused_decode and x.is_cuda and x.shape[0] <= 16
+        w8 = self._w8["layers"] if self._w8 is not None else None
         for li, layer in enumerate(self.gpt.layers):
-            y = _layer_decode_fused(layer, x, cache, li, wpos, after) \
-                if fused and _fusable(layer) else None
+            if fused and _fusable(layer):
+                y = _layer_decode_fused(layer, x, cache, li, wpos, after, w8[li]) if w8 \
+                    else _layer_decode_fused(layer, x, cache, li, wpos, after)
+            else:
+                y = None
             x = y if y is not None else _layer_decode(layer, x, cache, li, wpos, after)
         x = self.gpt.final_ln(x)
-        return self._logits(x[:, 0])
+        return self._logits(x[:, 0], self._w8["head"] if self._w8 is not None else None)
 
-    def _logits(self, h):
+    def _logits(self, h, q8=None):
+        """``q8``: the int8 copy of the tied table (decode steps; the prefill's
+        last-token logits use the 16-bit table like the rest of the prefill)."""
         w = self.gpt.embeddings.word_embeddings.weight
         logits = None
         if self.fused_decode and topo.mp_world_size() == 1:
             from ....ops import gemm as G
-            logits = G.decode_linear(h.contiguous(), w)
+            if q8 is not None:
+                logits = G.decode_linear_w8(h.contiguous(), q8[0], q8[1])
+            if logits is None:
+                logits = G.decode_linear(h.contiguous(), w)
         if logits is None:
             logits = F.linear(h, w)
         if topo.mp_world_size() > 1:
@@ -444,6 +528,7 @@ class GPTForGeneration(torch.nn.Module):
         Returns (generated ids [B, T], scores [B]); with ``decode_strategy:
         beam_search`` see ``_beam_search``."""
         self.eval()
+        self._w8_refresh()  # before the prefill and any graph capture
         if self.decode_strategy == "beam_search":
             return self._beam_search(input_ids, lens, max_length)
         dev = input_ids.device

@@ -4,7 +4,7 @@ from .elementwise import bias_gelu, bias_dropout_add, dropout  # noqa: F401
 from .attention import (flash_attention, flash_attention_qkvpacked, attention_reference,  # noqa: F401
                         decode_attention, beam_decode_attention)
 from .loss_embed import softmax_cross_entropy, embedding  # noqa: F401
-from .quant import fake_quant  # noqa: F401
+from .quant import fake_quant, quantize_weight_int8, dequantize_weight_int8  # noqa: F401
 from .sampling import fused_sample  # noqa: F401
 from .softmax import (fused_softmax, softmax_mask_fuse,  # noqa: F401
                       softmax_mask_fuse_upper_triangle)

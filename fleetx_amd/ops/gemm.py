@@ -481,3 +481,63 @@ def decode_linear(x, weight, bias=None, epi=GV_BIAS, res=None, qkv_cache=None, l
         return None
     _lib.maybe_sync()
     return y
+
+
+def decode_linear_w8(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, qkv_cache=None, ln=None):
+    """``decode_linear`` with a weight-only int8 weight (csrc/kernels/
+    decode_gemv_w8.hip): ``x [M, K] @ (wq[N, K] * wscale[N, None])^T`` with
+    ``wq`` int8 and ``wscale`` fp32 from ``ops.quantize_weight_int8``; the
+    int8 values are converted to ``x.dtype`` in registers (exactly), the
+    products accumulate in fp32, ``wscale`` multiplies the accumulator and the
+    epilogue ``epi`` / LayerNorm prologue ``ln`` are those of ``decode_linear``.
+
+    Returns the output, or None when the kernel does not cover the call (the
+    caller then uses the 16-bit weight)."""
+    if not x.is_cuda or x.dim() != 2 or x.shape[0] < 1 or x.shape[0] > 16 \
+            or x.dtype not in (torch.bfloat16, torch.float16):
+        return None
+    M, K = x.shape
+    if wq.dim() != 2 or wq.dtype != torch.int8 or not wq.is_cuda or wq.shape[1] != K:
+        return None
+    N = wq.shape[0]
+    if wq.stride(1) != 1 or x.stride(1) != 1 or K % 1024 or x.stride(0) % 8 or wq.stride(0) % 16 \
+            or wq.data_ptr() % 16 or x.data_ptr() % 16:
+        return None
+    if wscale.dtype != torch.float32 or not wscale.is_cuda or wscale.numel() != N \
+            or not wscale.is_contiguous():
+        return None
+    if bias is not None and (bias.dtype != x.dtype or bias.numel() != N
+                             or not bias.is_contiguous()):
+        return None
+    if ln is not None and (ln[0].dtype != x.dtype or ln[1] is None or ln[1].dtype != x.dtype
+                           or not ln[0].is_contiguous() or not ln[1].is_contiguous()
+                           or ln[0].numel() != K or ln[1].numel() != K
+                           or epi not in (GV_GELU, GV_QKV)):
+        return None
+    k = _lib.kernels()
+    kc = vc = pos = None
+    heads = hd = maxlen = 0
+    if epi == GV_QKV:
+        kc, vc, pos = qkv_cache
+        maxlen, heads, hd = kc.shape[1], kc.shape[2], kc.shape[3]
+        assert N == 3 * heads * hd and kc.is_contiguous() and vc.is_contiguous()
+        assert kc.shape == vc.shape and kc.shape[0] >= M and kc.dtype == x.dtype == vc.dtype
+        assert pos.dtype == torch.int64 and pos.numel() == M and pos.is_contiguous()
+        y = torch.empty(M, heads * hd, device=x.device, dtype=x.dtype)
+    else:
+        y = torch.empty(M, N, device=x.device, dtype=x.dtype)
+    if epi == GV_RES:
+        assert res is not None and res.shape == (M, N) and res.stride(1) == 1 \
+            and res.dtype == x.dtype
+    nb = k.decode_gemv_w8(_lib.dt_code(x.dtype), int(epi), M, N, K, x.data_ptr(), x.stride(0),
+                          wq.data_ptr(), wq.stride(0), wscale.data_ptr(), _lib.ptr(bias),
+                          _lib.ptr(res) if epi == GV_RES else 0,
+                          res.stride(0) if epi == GV_RES else 0, y.data_ptr(), y.stride(0),
+                          _lib.ptr(kc), _lib.ptr(vc), _lib.ptr(pos), heads, hd, maxlen,
+                          _lib.ptr(ln[0]) if ln is not None else 0,
+                          _lib.ptr(ln[1]) if ln is not None else 0,
+                          float(ln[2]) if ln is not None else 0.0, _lib.stream())
+    if nb == 0:
+        return None
+    _lib.maybe_sync()
+    return y

@@ -3,6 +3,9 @@
 Reference P11 / K23: paddleslim QAT with ``abs_max`` weight quantisation and
 ``moving_average_abs_max`` activation quantisation at 8 bits
 (``pretrain_gpt_345M_mp8_qat.yaml:35-44``).
+
+Also the per-row weight-only int8 quantiser whose output the decode GEMV
+consumes (``quantize_weight_int8`` / ``ops.gemm.decode_linear_w8``).
 """
 import torch
 
@@ -39,3 +42,24 @@ class _FakeQuant(torch.autograd.Function):
 def fake_quant(x, scale, bits=8):
     """Quantise-dequantise ``x`` with the per-tensor ``scale`` (device scalar)."""
     return _FakeQuant.apply(x, scale.float().reshape(1), bits)
+
+
+# ----------------------------------------------------------------------------
+# weight-only int8 for decoding (consumed by ops.gemm.decode_linear_w8)
+# ----------------------------------------------------------------------------
+def quantize_weight_int8(w):
+    """Symmetric int8 quantisation of ``w [N, K]`` with one scale per output
+    row: ``scale[n] = max|w[n, :]| / 127`` (fp32; 1 for an all-zero row) and
+    ``q = clamp(rint(w / scale), -127, 127)``.  Returns ``(q int8 [N, K]
+    contiguous, scale fp32 [N])``.  Plain torch ops: it runs once per weight."""
+    assert w.dim() == 2 and w.is_floating_point()
+    wf = w.detach().float()
+    amax = wf.abs().amax(dim=1)
+    scale = torch.where(amax > 0, amax / 127.0, torch.ones_like(amax))
+    q = torch.clamp(torch.round(wf / scale[:, None]), -127, 127).to(torch.int8)
+    return q.contiguous(), scale.contiguous()
+
+
+def dequantize_weight_int8(q, scale, dtype=torch.float32):
+    """``q * scale[:, None]`` computed in fp32 and rounded once to ``dtype``."""
+    return (q.float() * scale.float()[:, None]).to(dtype)

@@ -2,7 +2,12 @@
 weight-stream TB/s for the decoder-layer shapes of GPT 1.3B / 6.7B, against
 hipBLASLt (F.linear) on the same operands.  
 
-    python tools/bench_gemv.py [--m 1 8 16]"""
+    python tools/bench_gemv.py [--m 1 8 16]
+    python tools/bench_gemv.py --w8 [--m 1 4 16] [--repeat 2]
+
+``--w8`` times the weight-only int8 GEMV (csrc/kernels/decode_gemv_w8.hip)
+against the 16-bit one, alternating in one process on weights streamed from
+HBM (each series replayed from a HIP graph, so the figure is GPU time); ``--repeat`` runs each series that many times."""
 import argparse
 import json
 import os
@@ -30,13 +35,66 @@ def timeit(fn, iters=200):
     return a.elapsed_time(b) * 1000.0 / iters
 
 
+def time_graph(call, ncopy, iters=20):
+    """us per call of ``call(i)`` (i cycles over the weight copies), replayed
+    from a captured HIP graph of >= 32 calls: at 5-10 us per kernel an eager
+    loop times the Python wrapper, not the GPU."""
+    ncall = -(-32 // ncopy) * ncopy
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for i in range(ncopy):
+            call(i)
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        for i in range(ncall):
+            call(i % ncopy)
+    return timeit(graph.replay, iters) / ncall
+
+
+def main_w8(args, G):
+    from fleetx_amd import ops
+    for name in args.shapes or SHAPES:
+        N, K = SHAPES[name]
+        # the same count of copies for both (>= 1 GiB of 16-bit, >= 512 MiB of
+        # int8 weights: twice the 256 MB Infinity Cache), so every call streams from HBM
+        ncopy = max(2, -(-(1 << 30) // (N * K * 2)))
+        ws = [(torch.randn(N, K, device="cuda") * K ** -0.5).bfloat16() for _ in range(ncopy)]
+        qs = [ops.quantize_weight_int8(w) for w in ws]
+        b = torch.randn(N, device="cuda").bfloat16()
+        for M in args.m:
+            x = torch.randn(M, K, device="cuda").bfloat16()
+            assert G.decode_linear_w8(x, qs[0][0], qs[0][1], b) is not None
+            us16, us8 = [], []
+            for _ in range(args.repeat):
+                us16.append(time_graph(lambda i: G.decode_linear(x, ws[i], b), ncopy))
+                us8.append(time_graph(lambda i: G.decode_linear_w8(x, *qs[i], b), ncopy))
+            m16, m8 = min(us16), min(us8)
+            print(json.dumps({"shape": name, "M": M, "N": N, "K": K,
+                              "gemv16_us": [round(u, 2) for u in us16],
+                              "gemv_w8_us": [round(u, 2) for u in us8],
+                              "gemv16_TB_s": round(N * K * 2 / m16 / 1e6, 2),
+                              "gemv_w8_TB_s": round(N * K / m8 / 1e6, 2),
+                              "speedup": round(m16 / m8, 3),
+                              "spread16_pct": round(100 * (max(us16) - m16) / m16, 2)}),
+                  flush=True)
+        del ws, qs
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--m", type=int, nargs="+", default=[1, 16])
     ap.add_argument("--warm", action="store_true",
                     help="also time a weight resident in the Infinity Cache")
+    ap.add_argument("--w8", action="store_true", help="16-bit vs weight-only int8 GEMV")
+    ap.add_argument("--repeat", type=int, default=2, help="--w8: runs of each series")
+    ap.add_argument("--shapes", nargs="+", default=None, choices=sorted(SHAPES))
     args = ap.parse_args()
     from fleetx_amd.ops import gemm as G
+    if args.w8:
+        return main_w8(args, G)
     for name, (N, K) in SHAPES.items():
         # enough weight copies (>= 1 GiB) that successive calls stream from HBM,
         # as in a decode step over all layers, not from the 256 MB Infinity Cache

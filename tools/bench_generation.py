@@ -4,9 +4,13 @@ epilogues).  Random-init weights, bf16.
 
     python tools/bench_generation.py [--model gpt3-1.3B] [--batch 1 8 16] [--tokens 64]
                                      [--strategy beam_search --num-beams 4]
+                                     [--weight-quant int8 [--repeat 2]]
 
 One JSON line per (batch, fused): ms/token, tokens/s and the effective weight
-stream rate (parameter bytes / ms per token)."""
+stream rate (parameter bytes / ms per token).  ``--weight-quant int8`` adds the
+weight-only int8 decode path to every series, alternating with the 16-bit
+one in the same process; ``--repeat`` runs each series that many times (the
+spread of the 16-bit repeats is the yardstick for any difference)."""
 import argparse
 import json
 import os
@@ -30,6 +34,9 @@ def main():
     ap.add_argument("--strategy", default="greedy_search",
                     choices=["greedy_search", "sampling", "beam_search"])
     ap.add_argument("--num-beams", type=int, default=1)
+    ap.add_argument("--weight-quant", default=None, choices=["int8"],
+                    help="also run the fused decode on weight-only int8 copies")
+    ap.add_argument("--repeat", type=int, default=1)
     args = ap.parse_args()
     from fleetx_amd.models.language_model.gpt.model import GPTConfig, GPTForPretraining
     from fleetx_amd.models.language_model.gpt.generation import GPTForGeneration
@@ -41,10 +48,13 @@ def main():
     nbytes = sum(p.numel() * p.element_size() for p in model.parameters())
     for B in args.batch:
         prompt = torch.randint(0, 50304, (B, args.prompt), device="cuda")
-        for fused in ((True,) if args.fused_only else (False, True)):
+        series = [(f, None) for f in ((True,) if args.fused_only else (False, True))]
+        if args.weight_quant:
+            series.append((True, args.weight_quant))
+        for fused, wq in series * args.repeat:
             gen = GPTForGeneration(model, {"max_dec_len": args.tokens, "fused_decode": fused,
                                            "decode_strategy": args.strategy,
-                                           "num_beams": args.num_beams})
+                                           "num_beams": args.num_beams, "weight_quant": wq})
             gen.generate(prompt, max_length=8)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -60,7 +70,7 @@ def main():
                 os.environ.get("FLEETX_DECODE_PERSISTENT", "0") == "1"
             print(json.dumps({"model": args.model, "batch": B, "strategy": args.strategy,
                               "num_beams": args.num_beams if args.strategy == "beam_search" else 1,
-                              "fused_decode": fused,
+                              "fused_decode": fused, "weight_quant": wq,
                               "persistent_layers": persistent,
                               "ms_per_token": round(ms, 3),
                               "tokens_per_s": round(B * 1e3 / ms, 1),
