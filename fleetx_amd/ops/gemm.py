@@ -428,83 +428,30 @@ def wgrad_16(dy2, x2):
 
 
 # ----------------------------------------------------------------------------
-# decode-time skinny GEMM (csrc/kernels/decode_gemv.hip)
+# decode-time skinny GEMM (csrc/kernels/decode_gemv.h: one kernel template over
+# the weight operand -- decode_gemv.hip 16-bit, decode_gemv_w8.hip int8)
 # ----------------------------------------------------------------------------
 GV_BIAS, GV_GELU, GV_RES, GV_QKV = range(4)
 
 
-def decode_linear(x, weight, bias=None, epi=GV_BIAS, res=None, qkv_cache=None, ln=None):
-    """``x [M, K] @ weight[N, K]^T`` for M <= 16 rows on the weight-streaming
-    MFMA GEMV, with the epilogue ``epi``: GV_BIAS (+b), GV_GELU (gelu_tanh(+b)),
-    GV_RES (+b + res[M, N]) or GV_QKV (``qkv_cache = (k_cache, v_cache, pos)``:
-    the packed [heads][3][head_dim] output is scattered -- q returned as [M, H*D],
-    k/v written into the caches [M, maxlen, H, D] at ``pos`` [M]).
-
-    ``ln = (weight, bias, eps)`` (GV_GELU / GV_QKV): ``x`` is the residual
-    stream and its LayerNorm is fused into the GEMV as a prologue (the
-    decoder layer's LN1 / LN2 then cost no launch of their own).
-
-    Returns the output, or None when the kernel does not cover the shape (the
-    caller then uses the general GEMM)."""
-    if not x.is_cuda or x.dim() != 2 or x.shape[0] > 16 or x.dtype not in (torch.bfloat16,
-                                                                            torch.float16):
-        return None
-    M, K = x.shape
-    N = weight.shape[0]
-    if weight.dtype != x.dtype or weight.stride(1) != 1 or x.stride(1) != 1 or K % 1024:
-        return None
-    if ln is not None and (ln[0].dtype != x.dtype or ln[1] is None or ln[1].dtype != x.dtype
-                           or not ln[0].is_contiguous() or not ln[1].is_contiguous()
-                           or epi not in (GV_GELU, GV_QKV)):
-        return None
-    k = _lib.kernels()
-    kc = vc = pos = None
-    heads = hd = maxlen = 0
-    if epi == GV_QKV:
-        kc, vc, pos = qkv_cache
-        maxlen, heads, hd = kc.shape[1], kc.shape[2], kc.shape[3]
-        assert N == 3 * heads * hd and kc.is_contiguous() and vc.is_contiguous()
-        assert pos.dtype == torch.int64 and pos.numel() == M
-        y = torch.empty(M, heads * hd, device=x.device, dtype=x.dtype)
-    else:
-        y = torch.empty(M, N, device=x.device, dtype=x.dtype)
-    if res is not None:
-        assert res.shape == (M, N) and res.stride(1) == 1
-    nb = k.decode_gemv(_lib.dt_code(x.dtype), int(epi), M, N, K, x.data_ptr(), x.stride(0),
-                       weight.data_ptr(), weight.stride(0), _lib.ptr(bias), _lib.ptr(res),
-                       res.stride(0) if res is not None else 0, y.data_ptr(), y.stride(0),
-                       _lib.ptr(kc), _lib.ptr(vc), _lib.ptr(pos), heads, hd, maxlen,
-                       _lib.ptr(ln[0]) if ln is not None else 0,
-                       _lib.ptr(ln[1]) if ln is not None else 0,
-                       float(ln[2]) if ln is not None else 0.0, _lib.stream())
-    if nb == 0:
-        return None
-    _lib.maybe_sync()
-    return y
-
-
-def decode_linear_w8(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, qkv_cache=None, ln=None):
-    """``decode_linear`` with a weight-only int8 weight (csrc/kernels/
-    decode_gemv_w8.hip): ``x [M, K] @ (wq[N, K] * wscale[N, None])^T`` with
-    ``wq`` int8 and ``wscale`` fp32 from ``ops.quantize_weight_int8``; the
-    int8 values are converted to ``x.dtype`` in registers (exactly), the
-    products accumulate in fp32, ``wscale`` multiplies the accumulator and the
-    epilogue ``epi`` / LayerNorm prologue ``ln`` are those of ``decode_linear``.
-
-    Returns the output, or None when the kernel does not cover the call (the
-    caller then uses the 16-bit weight)."""
+def _decode_gemv(x, w, wscale, bias, epi, res, qkv_cache, ln):
+    """The body of ``decode_linear`` (``wscale`` None: ``w`` is a 16-bit weight
+    of ``x.dtype``) and ``decode_linear_w8`` (``w`` int8, ``wscale`` fp32 [N]):
+    the checks, the QKV unpacking, the output and the call.  None for a call
+    the kernel does not cover; malformed caches / residual assert."""
     if not x.is_cuda or x.dim() != 2 or x.shape[0] < 1 or x.shape[0] > 16 \
             or x.dtype not in (torch.bfloat16, torch.float16):
         return None
     M, K = x.shape
-    if wq.dim() != 2 or wq.dtype != torch.int8 or not wq.is_cuda or wq.shape[1] != K:
+    wdtype = x.dtype if wscale is None else torch.int8
+    if w.dim() != 2 or w.dtype != wdtype or not w.is_cuda or w.shape[1] != K:
         return None
-    N = wq.shape[0]
-    if wq.stride(1) != 1 or x.stride(1) != 1 or K % 1024 or x.stride(0) % 8 or wq.stride(0) % 16 \
-            or wq.data_ptr() % 16 or x.data_ptr() % 16:
+    N = w.shape[0]
+    if w.stride(1) != 1 or x.stride(1) != 1 or K % 1024 or x.stride(0) % 8 \
+            or (w.stride(0) * w.element_size()) % 16 or w.data_ptr() % 16 or x.data_ptr() % 16:
         return None
-    if wscale.dtype != torch.float32 or not wscale.is_cuda or wscale.numel() != N \
-            or not wscale.is_contiguous():
+    if wscale is not None and (wscale.dtype != torch.float32 or not wscale.is_cuda
+                               or wscale.numel() != N or not wscale.is_contiguous()):
         return None
     if bias is not None and (bias.dtype != x.dtype or bias.numel() != N
                              or not bias.is_contiguous()):
@@ -529,15 +476,48 @@ def decode_linear_w8(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, qkv_cache=
     if epi == GV_RES:
         assert res is not None and res.shape == (M, N) and res.stride(1) == 1 \
             and res.dtype == x.dtype
-    nb = k.decode_gemv_w8(_lib.dt_code(x.dtype), int(epi), M, N, K, x.data_ptr(), x.stride(0),
-                          wq.data_ptr(), wq.stride(0), wscale.data_ptr(), _lib.ptr(bias),
-                          _lib.ptr(res) if epi == GV_RES else 0,
-                          res.stride(0) if epi == GV_RES else 0, y.data_ptr(), y.stride(0),
-                          _lib.ptr(kc), _lib.ptr(vc), _lib.ptr(pos), heads, hd, maxlen,
-                          _lib.ptr(ln[0]) if ln is not None else 0,
-                          _lib.ptr(ln[1]) if ln is not None else 0,
-                          float(ln[2]) if ln is not None else 0.0, _lib.stream())
+    head = (_lib.dt_code(x.dtype), int(epi), M, N, K, x.data_ptr(), x.stride(0),
+            w.data_ptr(), w.stride(0))
+    tail = (_lib.ptr(bias), _lib.ptr(res) if epi == GV_RES else 0,
+            res.stride(0) if epi == GV_RES else 0, y.data_ptr(), y.stride(0),
+            _lib.ptr(kc), _lib.ptr(vc), _lib.ptr(pos), heads, hd, maxlen,
+            _lib.ptr(ln[0]) if ln is not None else 0, _lib.ptr(ln[1]) if ln is not None else 0,
+            float(ln[2]) if ln is not None else 0.0, _lib.stream())
+    if wscale is None:
+        nb = k.decode_gemv(*head, *tail)
+    else:
+        nb = k.decode_gemv_w8(*head, wscale.data_ptr(), *tail)
     if nb == 0:
         return None
     _lib.maybe_sync()
     return y
+
+
+def decode_linear(x, weight, bias=None, epi=GV_BIAS, res=None, qkv_cache=None, ln=None):
+    """``x [M, K] @ weight[N, K]^T`` for M <= 16 rows on the weight-streaming
+    MFMA GEMV, with the epilogue ``epi``: GV_BIAS (+b), GV_GELU (gelu_tanh(+b)),
+    GV_RES (+b + res[M, N]) or GV_QKV (``qkv_cache = (k_cache, v_cache, pos)``:
+    the packed [heads][3][head_dim] output is scattered -- q returned as [M, H*D],
+    k/v written into the caches [M, maxlen, H, D] at ``pos`` [M]).
+
+    ``ln = (weight, bias, eps)`` (GV_GELU / GV_QKV): ``x`` is the residual
+    stream and its LayerNorm is fused into the GEMV as a prologue (the
+    decoder layer's LN1 / LN2 then cost no launch of their own).
+
+    Returns the output, or None when the kernel does not cover the call (the
+    caller then uses the general GEMM)."""
+    return _decode_gemv(x, weight, None, bias, epi, res, qkv_cache, ln)
+
+
+def decode_linear_w8(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, qkv_cache=None, ln=None):
+    """``decode_linear`` with a weight-only int8 weight: ``x [M, K] @ (wq[N, K]
+    * wscale[N, None])^T`` with ``wq`` int8 and ``wscale`` fp32 from
+    ``ops.quantize_weight_int8``; the int8 values are converted to ``x.dtype``
+    in registers (exactly), the products accumulate in fp32 and ``wscale``
+    multiplies the accumulator before the bias.
+
+    Returns the output, or None when the kernel does not cover the call (the
+    caller then uses the 16-bit weight)."""
+    if wscale is None:
+        return None
+    return _decode_gemv(x, wq, wscale, bias, epi, res, qkv_cache, ln)

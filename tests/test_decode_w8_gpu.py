@@ -7,6 +7,8 @@ import copy
 import pytest
 import torch
 
+from tests.gemv_cases import _int_case
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 DTYPES = [torch.bfloat16, torch.float16]
@@ -19,19 +21,9 @@ def _rel(a, b):
 # ----------------------------------------------------------------------------
 # 1. exact layout test: integer data, every partial sum an integer < 2^24, so
 #    fp32 accumulation is exact in any order and the output must equal the
-#    float64 result rounded once
+#    float64 result rounded once (data: tests/gemv_cases.py, shared with the
+#    16-bit twins in test_decode_gpu.py)
 # ----------------------------------------------------------------------------
-def _int_case(M, N, K, seed):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randint(-4, 5, (M, K), generator=g).double()
-    q = torch.randint(-127, 128, (N, K), generator=g).to(torch.int8)
-    b = torch.randint(-8, 9, (N,), generator=g).double()
-    res = torch.randint(-8, 9, (M, N), generator=g).double()
-    acc = x @ q.double().t()
-    assert float(acc.abs().max()) < 2 ** 24
-    return x, q, b, res, acc * 2.0 ** -7 + b
-
-
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("M,N,K", [(3, 1000, 1024), (16, 96, 2048), (1, 4096, 4096)])
 def test_w8_exact_bias_and_residual(dtype, M, N, K):
@@ -162,6 +154,29 @@ def test_w8_fused_layernorm(M, N, K, epi):
         assert _rel(y.view(M, H, D), r[:, :, 0]) < 8e-3
         assert _rel(kc[ar, pos], r[:, :, 1]) < 8e-3
         assert _rel(vc[ar, pos], r[:, :, 2]) < 8e-3
+
+
+def test_w8_fused_layernorm_lds_opt_in_boundary():
+    """M = 3, K = 10240: the normalised rows take 61488 B of dynamic LDS, under
+    64 KiB alone but over it with the kernel's static 8192 B, so the launch
+    needs the large-LDS opt-in (recipe and bound of test_w8_fused_layernorm)."""
+    from fleetx_amd import ops
+    from fleetx_amd.ops import gemm as G
+    M, N, K = 3, 96, 10240
+    assert M * (K + 8) * 2 <= 65536 < M * (K + 8) * 2 + 8192
+    g = torch.Generator(device=DEV).manual_seed(M + N + K + G.GV_GELU)
+    x = (3.0 + torch.randn(M, K, device=DEV, generator=g)).bfloat16()
+    w = (torch.randn(N, K, device=DEV, generator=g) * K ** -0.5).bfloat16()
+    b = torch.randn(N, device=DEV, generator=g).bfloat16()
+    lw = (1 + 0.1 * torch.randn(K, device=DEV, generator=g)).bfloat16()
+    lb = (0.1 * torch.randn(K, device=DEV, generator=g)).bfloat16()
+    q, scale = ops.quantize_weight_int8(w)
+    xn = torch.nn.functional.layer_norm(x.float(), (K,), lw.float(), lb.float(), 1e-5)
+    ref = xn.bfloat16().float() @ (q.float() * scale[:, None]).t() + b.float()
+    ref = torch.nn.functional.gelu(ref, approximate="tanh")
+    y = G.decode_linear_w8(x, q, scale, b, G.GV_GELU, ln=(lw, lb, 1e-5))
+    assert y is not None
+    assert _rel(y, ref) < 8e-3, _rel(y, ref)   # .item() inside waits for the kernel
 
 
 # ----------------------------------------------------------------------------
