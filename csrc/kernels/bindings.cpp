@@ -220,6 +220,19 @@ PYBIND11_MODULE(_kernels, m) {
     return fx_sample(dt, CP(logits), ld, B, V, inv_temp, top_k, top_p, F(u),
                      reinterpret_cast<int64_t*>(ids), F(lse), F(probs), S(st));
   });
+  m.def("select", [](ptr logits, long ld, int B, int V, int sampling, float inv_temp, int top_k,
+                     float top_p, ptr u, int n_steps, int eos, int pad, int min_len, float pen,
+                     float inv_pen, int bos, int feos, int feos_step, ptr seen, int words,
+                     ptr step, ptr unfinished, ptr finish_len, ptr scores, ptr out, ptr nxt,
+                     ptr cur, ptr lens, ptr st) {
+    return fx_select(F(logits), ld, B, V, sampling, inv_temp, top_k, top_p, F(u), n_steps, eos,
+                     pad, min_len, pen, inv_pen, bos, feos, feos_step,
+                     reinterpret_cast<unsigned int*>(seen), words, reinterpret_cast<int*>(step),
+                     reinterpret_cast<int*>(unfinished), reinterpret_cast<int*>(finish_len),
+                     F(scores), reinterpret_cast<int64_t*>(out), reinterpret_cast<int64_t*>(nxt),
+                     reinterpret_cast<int64_t*>(cur), reinterpret_cast<const int64_t*>(lens),
+                     S(st));
+  });
   m.def("decode_attn", [](int dt, ptr q, ptr kc, ptr vc, ptr out, ptr lens, int B, int H, int D,
                           int maxlen, int nsplit, ptr ws, long sqb, long sqh, long skb, long sks,
                           long skh, long sob, float scale, ptr st) {

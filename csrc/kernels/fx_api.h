@@ -80,6 +80,11 @@ int fx_gn_bwd_apply(int, const void*, const void*, const float*, const float*, c
 int fx_transpose16(int, const void*, void*, float*, int, int, long, long, hipStream_t);
 int fx_sample(int, const void*, long, int, int, float, int, float, const float*, int64_t*, float*,
               float*, hipStream_t);
+int fx_select(const float* logits, long ld_row, int B, int V, int sampling, float inv_temp,
+              int top_k, float top_p, const float* u, int n_steps, int eos, int pad, int min_len,
+              float pen, float inv_pen, int bos, int feos, int feos_step, unsigned int* seen,
+              int words, int* step, int* unfinished, int* finish_len, float* scores,
+              int64_t* out, int64_t* nxt, int64_t* cur, const int64_t* lens, hipStream_t);
 int fx_decode_attn(int, const void*, const void*, const void*, void*, const int*, int, int, int,
                    int, int, float*, long, long, long, long, long, long, float, hipStream_t);
 int fx_beam_decode_attn(int, const void*, const void*, const void*, const int*, const void*,

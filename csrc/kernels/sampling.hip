@@ -75,22 +75,18 @@ __device__ __forceinline__ float block_sum(float v, Shared& s) {
   return r;
 }
 
-template <typename T>
-__global__ __launch_bounds__(ST) void sample_kernel(const T* __restrict__ logits, long ld_row,
-                                                   int V, float inv_temp, int top_k, float top_p,
-                                                   const float* __restrict__ uniforms,
-                                                   int64_t* __restrict__ out_ids,
-                                                   float* __restrict__ out_lse,
-                                                   float* __restrict__ out_probs) {
-  __shared__ Shared s;
-  const int tid = threadIdx.x;
-  const long row = blockIdx.x;
-  const T* lg = logits + row * ld_row;
+// ---- the four phases, over a logit loader `load(i)` (raw logits in
+// sample_kernel, processed logits in select_kernel: one text for both)
 
-  // ---- 1. softmax denominators
+// 1. softmax denominators of load(i)/T (max `m`, 1/sum-exp `inv_se`) and the
+//    logsumexp of load(i) itself
+template <typename L>
+__device__ __forceinline__ void softmax_stats(const L& load, int V, float inv_temp, Shared& s,
+                                              float& m_out, float& inv_se, float& lse) {
+  const int tid = threadIdx.x;
   float m = -INFINITY, mraw = -INFINITY;
   for (int i = tid; i < V; i += ST) {
-    const float x = ld<T>(lg, i);
+    const float x = load(i);
     m = fmaxf(m, x * inv_temp);
     mraw = fmaxf(mraw, x);
   }
@@ -98,18 +94,23 @@ __global__ __launch_bounds__(ST) void sample_kernel(const T* __restrict__ logits
   const float mr = block_max(mraw, s);
   float se = 0.f, ser = 0.f;
   for (int i = tid; i < V; i += ST) {
-    const float x = ld<T>(lg, i);
+    const float x = load(i);
     se += __expf(x * inv_temp - m);
     ser += __expf(x - mr);
   }
   se = block_sum(se, s);
   ser = block_sum(ser, s);
-  const float inv_se = 1.f / se;
-  if (tid == 0 && out_lse) out_lse[row] = mr + __logf(ser);
-  auto prob = [&](int i) { return __expf(ld<T>(lg, i) * inv_temp - m) * inv_se; };
+  m_out = m;
+  inv_se = 1.f / se;
+  lse = mr + __logf(ser);
+}
 
-  // ---- 2. top-k threshold (radix select on the probability bits)
-  unsigned int kth = 0u;  // keep p_bits >= kth
+// 2. top-k threshold (radix select on the probability bits): keep p_bits >= kth
+template <typename P>
+__device__ __forceinline__ unsigned int topk_threshold(const P& prob, int V, int top_k,
+                                                       Shared& s) {
+  const int tid = threadIdx.x;
+  unsigned int kth = 0u;
   if (top_k > 0 && top_k < V) {
     if (tid == 0) {
       s.sel_prefix = 0u;
@@ -140,8 +141,14 @@ __global__ __launch_bounds__(ST) void sample_kernel(const T* __restrict__ logits
     __syncthreads();
     kth = s.sel_prefix;
   }
+  return kth;
+}
 
-  // ---- 3. top-p threshold over the top-k survivors' mass
+// 3. top-p threshold over the top-k survivors' mass
+template <typename P>
+__device__ __forceinline__ unsigned int topp_threshold(const P& prob, int V, float top_p,
+                                                       unsigned int kth, Shared& s) {
+  const int tid = threadIdx.x;
   unsigned int pth = 0u;
   if (top_p < 1.f) {
     if (tid == 0) {
@@ -188,9 +195,15 @@ __global__ __launch_bounds__(ST) void sample_kernel(const T* __restrict__ logits
     __syncthreads();
     pth = s.sel_k == 1u ? 0u : s.sel_prefix;
   }
-  const unsigned int thr = kth > pth ? kth : pth;
+  return pth;
+}
 
-  // ---- 4. inverse-CDF draw in index order
+// 4. inverse-CDF draw in index order with the uniform `u`; every thread
+//    returns the pick (0 when nothing survives)
+template <typename P>
+__device__ __forceinline__ int draw_token(const P& prob, int V, unsigned int thr, float u,
+                                          float* __restrict__ probs_row, Shared& s) {
+  const int tid = threadIdx.x;
   const int chunk = (V + ST - 1) / ST;
   const int lo = min(V, tid * chunk), hi = min(V, lo + chunk);
   float part = 0.f;
@@ -202,7 +215,7 @@ __global__ __launch_bounds__(ST) void sample_kernel(const T* __restrict__ logits
       part += p;
       last = i;
     }
-    if (out_probs) out_probs[row * (long)V + i] = keep ? p : 0.f;
+    if (probs_row) probs_row[i] = keep ? p : 0.f;
   }
   s.scan[tid] = part;
   if (tid == 0) s.pick = -1;
@@ -215,7 +228,7 @@ __global__ __launch_bounds__(ST) void sample_kernel(const T* __restrict__ logits
     __syncthreads();
   }
   const float total = s.scan[ST - 1];
-  const float target = uniforms[row] * total;
+  const float target = u * total;
   const float excl = s.scan[tid] - part;
   if (part > 0.f && target >= excl && target < excl + part) {
     float c = excl;
@@ -234,7 +247,154 @@ __global__ __launch_bounds__(ST) void sample_kernel(const T* __restrict__ logits
   __syncthreads();
   if (s.pick < 0 && last >= 0) atomicMax(&s.pick, last);  // rounding: u*total past the end
   __syncthreads();
-  if (tid == 0) out_ids[row] = s.pick < 0 ? 0 : s.pick;
+  return s.pick < 0 ? 0 : s.pick;
+}
+
+// phases 1-4 on load(i); returns the pick, `lse` is the logsumexp of load(i)
+template <typename L>
+__device__ __forceinline__ int sample_row(const L& load, int V, float inv_temp, int top_k,
+                                          float top_p, float u, float* __restrict__ probs_row,
+                                          Shared& s, float& lse) {
+  float m, inv_se;
+  softmax_stats(load, V, inv_temp, s, m, inv_se, lse);
+  auto prob = [&](int i) { return __expf(load(i) * inv_temp - m) * inv_se; };
+  const unsigned int kth = topk_threshold(prob, V, top_k, s);
+  const unsigned int pth = topp_threshold(prob, V, top_p, kth, s);
+  return draw_token(prob, V, kth > pth ? kth : pth, u, probs_row, s);
+}
+
+template <typename T>
+__global__ __launch_bounds__(ST) void sample_kernel(const T* __restrict__ logits, long ld_row,
+                                                   int V, float inv_temp, int top_k, float top_p,
+                                                   const float* __restrict__ uniforms,
+                                                   int64_t* __restrict__ out_ids,
+                                                   float* __restrict__ out_lse,
+                                                   float* __restrict__ out_probs) {
+  __shared__ Shared s;
+  const long row = blockIdx.x;
+  const T* lg = logits + row * ld_row;
+  auto load = [&](int i) { return ld<T>(lg, i); };
+  float lse;
+  const int pick = sample_row(load, V, inv_temp, top_k, top_p, uniforms[row],
+                              out_probs ? out_probs + row * (long)V : nullptr, s, lse);
+  if (threadIdx.x == 0) {
+    if (out_lse) out_lse[row] = lse;
+    out_ids[row] = pick;
+  }
+}
+
+// ---------------------------------------------------------------- selection
+// One decode step's token selection, state in device memory (K18, K19): the
+// logits processors applied on the load, the pick (greedy or phases 1-4
+// above), then the bookkeeping the host loop does between two decode steps.
+// A row belongs to one block, so the epilogue is one thread's plain stores.
+struct SelectArgs {
+  const float* logits;      // [B, V] fp32, read-only
+  long ld_row;
+  int V, B;
+  int sampling;             // 0: greedy, 1: top-k / top-p sampling
+  float inv_temp;
+  int top_k;
+  float top_p;
+  const float* u;           // [n_steps, B] uniforms (sampling)
+  int n_steps;
+  int eos, pad;             // eos < 0: none
+  int min_len;              // 0: off
+  int use_pen;
+  float pen, inv_pen;
+  int bos;                  // forced at step 0 (< 0: off)
+  int feos, feos_step;      // forced at step == feos_step (feos < 0: off)
+  unsigned int* seen;       // [B, words] bitmap of each row's history
+  int words;
+  int* step;                // [B]
+  int* unfinished;          // [B]
+  int* finish_len;          // [B]
+  float* scores;            // [B]
+  int64_t* out;             // [B, n_steps]
+  int64_t* nxt;             // [B] the decode graph's static inputs
+  int64_t* cur;
+  const int64_t* lens;      // [B]
+};
+
+// the processed logit x'(i), in the order of GPTForGeneration._processors()
+struct ProcLoad {
+  const float* lg;
+  const unsigned int* seen;
+  int mask_eos;   // min length active: this index gets -1e9 (< 0: off)
+  int force;      // forced BOS / EOS: this index gets 0, the rest -1e9 (< 0: off)
+  int use_pen;
+  float pen, inv_pen;
+  __device__ __forceinline__ float operator()(int i) const {
+#pragma clang fp contract(off)
+    if (force >= 0) return i == force ? 0.f : -1e9f;
+    float x = lg[i];
+    if (i == mask_eos) x = -1e9f;
+    // rounded products (never contracted into a consumer's add): bitwise torch's
+    // GPU `x * pen` and `x / pen`, the latter being `x * fp32(1 / pen)` there
+    if (use_pen && ((seen[i >> 5] >> (i & 31)) & 1u))
+      x = x < 0.f ? x * pen : x * inv_pen;
+    return x;
+  }
+};
+
+__global__ __launch_bounds__(ST) void select_kernel(SelectArgs a) {
+  __shared__ Shared s;
+  const int tid = threadIdx.x;
+  const int row = blockIdx.x;
+  const int step = a.step[row];
+  if (step >= a.n_steps) return;  // out / u hold n_steps columns
+  const int unf = a.unfinished[row];
+  unsigned int* seen = a.seen + (long)row * a.words;
+  ProcLoad load;
+  load.lg = a.logits + row * a.ld_row;
+  load.seen = seen;
+  load.mask_eos = (a.eos >= 0 && step < a.min_len) ? a.eos : -1;
+  load.force = (a.feos >= 0 && step == a.feos_step) ? a.feos
+               : (a.bos >= 0 && step == 0)          ? a.bos
+                                                    : -1;
+  load.use_pen = a.use_pen;
+  load.pen = a.pen;
+  load.inv_pen = a.inv_pen;
+  int pick = 0;
+  float lse = 0.f;
+  if (unf) {  // a finished row emits pad: nothing to pick
+    if (a.sampling) {
+      pick = sample_row(load, a.V, a.inv_temp, a.top_k, a.top_p, a.u[(long)step * a.B + row],
+                        nullptr, s, lse);
+    } else {
+      // max, then sum-exp and the lowest index that holds the max
+      float m = -INFINITY;
+      for (int i = tid; i < a.V; i += ST) m = fmaxf(m, load(i));
+      m = block_max(m, s);
+      if (tid == 0) s.pick = a.V;
+      __syncthreads();
+      float se = 0.f;
+      int first = a.V;
+      for (int i = tid; i < a.V; i += ST) {
+        const float x = load(i);
+        se += __expf(x - m);
+        if (x == m) first = min(first, i);
+      }
+      se = block_sum(se, s);
+      if (first < a.V) atomicMin(&s.pick, first);
+      __syncthreads();
+      pick = s.pick < a.V ? s.pick : 0;
+      lse = m + __logf(se);
+    }
+  }
+  if (tid == 0) {
+    const int tok = unf ? pick : a.pad;
+    if (unf) a.scores[row] += load(pick) - lse;
+    a.out[(long)row * a.n_steps + step] = tok;
+    if (tok >= 0 && tok < a.V) seen[tok >> 5] |= 1u << (tok & 31);
+    if (unf && tok == a.eos) {
+      a.unfinished[row] = 0;
+      a.finish_len[row] = step + 1;
+    }
+    a.nxt[row] = tok;
+    a.cur[row] = a.lens[row] + step;
+    a.step[row] = step + 1;
+  }
 }
 
 }  // namespace
@@ -252,5 +412,28 @@ extern "C" int fx_sample(int dtype, const void* logits, long ld_row, int B, int 
                                               out_probs);
   else
     return -1;
+  return 0;
+}
+
+extern "C" int fx_select(const float* logits, long ld_row, int B, int V, int sampling,
+                         float inv_temp, int top_k, float top_p, const float* u, int n_steps,
+                         int eos, int pad, int min_len, float pen, float inv_pen, int bos,
+                         int feos, int feos_step, unsigned int* seen, int words, int* step,
+                         int* unfinished, int* finish_len, float* scores, int64_t* out,
+                         int64_t* nxt, int64_t* cur, const int64_t* lens, hipStream_t st) {
+  if (B <= 0 || V <= 0 || n_steps <= 0) return 0;
+  if (words < (V + 31) / 32 || (sampling && !u)) return -1;
+  if (pad < 0 || pad >= V || eos >= V || bos >= V || feos >= V) return -2;
+  SelectArgs a;
+  a.logits = logits, a.ld_row = ld_row, a.V = V, a.B = B;
+  a.sampling = sampling, a.inv_temp = inv_temp, a.top_k = top_k, a.top_p = top_p;
+  a.u = u, a.n_steps = n_steps;
+  a.eos = eos, a.pad = pad, a.min_len = min_len;
+  a.use_pen = pen != 1.f, a.pen = pen, a.inv_pen = inv_pen;
+  a.bos = bos, a.feos = feos, a.feos_step = feos_step;
+  a.seen = seen, a.words = words, a.step = step, a.unfinished = unfinished;
+  a.finish_len = finish_len, a.scores = scores, a.out = out, a.nxt = nxt, a.cur = cur;
+  a.lens = lens;
+  select_kernel<<<B, ST, 0, st>>>(a);
   return 0;
 }

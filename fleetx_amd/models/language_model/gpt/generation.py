@@ -330,6 +330,11 @@ class _GraphedDecodeStep:
     def __call__(self, nxt, cur):
         self.nxt.copy_(nxt)
         self.cur.copy_(cur)
+        return self._capture_or_replay()
+
+    def _capture_or_replay(self):
+        """First call: run the step eagerly on a side stream (that token's real
+        work) and capture it; afterwards replay.  Returns the step's output."""
         if self.graph is None:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
@@ -358,6 +363,26 @@ class _GraphedBeamStep(_GraphedDecodeStep):
 
     def _run(self):
         return self.gen._beam_decode_step(self.nxt, self.cur, self.cache, self.slot, self.glens)
+
+
+class _GraphedSelectStep(_GraphedDecodeStep):
+    """Decode step and token selection (``ops.select_token``) as one graph:
+    the selection writes the step's inputs ``nxt`` / ``cur`` itself (they are
+    the state's tensors), so a token is one replay with no host copy and no
+    host read."""
+
+    def __init__(self, gen, cache, state):
+        super().__init__(gen, cache, state.nxt.shape[0])
+        self.state = state
+        self.nxt, self.cur = state.nxt, state.cur
+
+    def __call__(self):
+        self._capture_or_replay()
+
+    def _run(self):
+        logits = self.gen._decode_step(self.nxt, self.cur, self.cache)
+        ops.select_token(logits, self.state)
+        return logits
 
 
 class GPTForGeneration(torch.nn.Module):
@@ -394,6 +419,10 @@ class GPTForGeneration(torch.nn.Module):
         self._w8 = None        # {"layers": [{name: (q, scale)}], "head": (q, scale)}
         self._w8_src = []      # (weight, _version, data_ptr) of every quantised weight
         self._w8_warned = False
+        # token selection on the device, one graph replay per token (sampling / greedy)
+        self.device_loop = bool(c.get("device_loop", False))
+        self.eos_poll = max(1, int(c.get("eos_poll", 8)))
+        self._device_loop_warned = False
         if self.decode_strategy not in ("sampling", "greedy_search", "beam_search"):
             raise ValueError("decode_strategy must be sampling, greedy_search or beam_search")
         if self.decode_strategy == "beam_search":
@@ -526,7 +555,16 @@ class GPTForGeneration(torch.nn.Module):
     def generate(self, input_ids, lens=None, max_length=None, seed=None):
         """input_ids: [B, S] right-padded; lens: [B] prompt lengths.
         Returns (generated ids [B, T], scores [B]); with ``decode_strategy:
-        beam_search`` see ``_beam_search``."""
+        beam_search`` see ``_beam_search``.
+
+        With ``device_loop`` (sampling / greedy only) the processors, the pick
+        and the EOS bookkeeping run in one kernel behind the decode step
+        (``ops.select_token``) and the host reads ``unfinished`` only every
+        ``eos_poll`` tokens; ids and scores are those of the default loop.
+        Seeded sampling is reproducible under ``device_loop`` but draws its
+        uniforms in a different order (one ``[N, B]`` table up front; on the
+        CPU an inverse-CDF draw instead of ``torch.multinomial``), so a seed
+        does not give the default loop's tokens."""
         self.eval()
         self._w8_refresh()  # before the prefill and any graph capture
         if self.decode_strategy == "beam_search":
@@ -557,9 +595,15 @@ class GPTForGeneration(torch.nn.Module):
         x = self.gpt.final_ln(x)
         last = x[torch.arange(B, device=dev), lens - 1]
         logits = self._logits(last)
-        procs = self._processors(max_new)
         eos = self.eos_token_id
         pad = self.pad_token_id if self.pad_token_id is not None else (eos if eos is not None else 0)
+        if self.device_loop:
+            if topo.mp_world_size() == 1:
+                return self._device_loop(input_ids, lens, logits, cache, max_new, pad, gen)
+            if not self._device_loop_warned:
+                warnings.warn("device_loop is ignored under tensor parallelism")
+                self._device_loop_warned = True
+        procs = self._processors(max_new)
         unfinished = torch.ones(B, dtype=torch.bool, device=dev)
         scores = torch.zeros(B, device=dev)
         out_tokens = []
@@ -610,6 +654,41 @@ class GPTForGeneration(torch.nn.Module):
         if not out_tokens:
             return torch.zeros(B, 0, dtype=torch.long, device=dev), scores
         return torch.stack(out_tokens, 1), scores
+
+    def _device_loop(self, input_ids, lens, logits, cache, max_new, pad, gen):
+        """The sampling / greedy loop with the selection on the device
+        (``device_loop``): selection 0 on the prefill ``logits``, then up to
+        ``N - 1`` times {decode step -> selection}, replayed from one HIP
+        graph.  ``N`` is the number of selections the host loop makes (the
+        bound of ``_beam_search``).  Replays after the last row finished write
+        pads past ``max(finish_len)`` and are trimmed."""
+        dev = input_ids.device
+        B = input_ids.shape[0]
+        eos = self.eos_token_id
+        N = max(0, min(max_new, self.gpt.cfg.max_position_embeddings - int(lens.max().item())))
+        if N == 0:
+            return (torch.zeros(B, 0, dtype=torch.long, device=dev), torch.zeros(B, device=dev))
+        greedy = self.decode_strategy == "greedy_search"
+        u = None if greedy else torch.rand(N, B, generator=gen, device=dev)
+        state = ops.SelectState(
+            input_ids, lens, logits.shape[-1], N, greedy=greedy, temperature=self.temperature,
+            top_k=self.top_k, top_p=self.top_p, eos=eos, pad=pad, min_len=self.min_length,
+            penalty=self.repetition_penalty, forced_bos=self.forced_bos_token_id,
+            forced_eos=self.forced_eos_token_id, max_len=max_new, u=u)
+        ops.select_token(logits, state)
+        step = None
+        if self.use_hip_graph and dev.type == "cuda":
+            step = _GraphedSelectStep(self, cache, state)
+        for t in range(1, N):
+            if eos is not None and t % self.eos_poll == 0 \
+                    and not bool(state.unfinished.any()):
+                break
+            if step is not None:
+                step()
+            else:
+                ops.select_token(self._decode_step(state.nxt, state.cur, cache), state)
+        T = int(state.finish_len.max().item())
+        return state.out[:, :T], state.scores
 
     def _beam_search(self, input_ids, lens=None, max_length=None):
         """Beam search with ``nb = num_beams`` beams per sample on a

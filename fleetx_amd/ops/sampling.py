@@ -5,6 +5,10 @@ multinomial -> log_softmax/gather (reference ``single_model.py:907-988``).
 The uniforms come from a torch generator so seeded generation is
 reproducible; CPU tensors take the PyTorch reference path
 (``generation.top_k_filter`` / ``top_p_filter`` + ``torch.multinomial``).
+
+``select_token`` is the whole per-token selection on the device (logits
+processors, pick, EOS bookkeeping; ``Generation.device_loop``) on a
+``SelectState``.
 """
 import torch
 
@@ -55,3 +59,175 @@ def fused_sample(logits, temperature=1.0, top_k=0, top_p=1.0, generator=None,
         raise RuntimeError("fused sampling launch failed ({})".format(rc))
     _lib.maybe_sync()
     return (ids, lse, probs) if return_probs else (ids, lse)
+
+
+# ---------------------------------------------------------------------------
+# on-device token selection (K18, K19; select_kernel in csrc/kernels/sampling.hip)
+# ---------------------------------------------------------------------------
+def _pack_seen(tokens, vocab):
+    """Bitmap int32 [B, ceil(V/32)] (read as uint32 words) of the tokens in each
+    row of ``tokens`` [B, n]; the ``V % 32`` tail bits stay 0."""
+    B = tokens.shape[0]
+    words = (vocab + 31) // 32
+    bits = torch.zeros(B, words * 32, dtype=torch.bool, device=tokens.device)
+    bits.scatter_(1, tokens, True)
+    w = (bits.view(B, words, 32).long() << torch.arange(32, device=tokens.device)).sum(-1)
+    return torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)
+
+
+def unpack_seen(seen, vocab):
+    """The boolean set [B, V] that the bitmap ``seen`` holds."""
+    sh = torch.arange(32, device=seen.device, dtype=torch.int32)
+    bits = (seen[:, :, None] >> sh) & 1
+    return bits.bool().view(seen.shape[0], -1)[:, :vocab]
+
+
+class SelectState:
+    """The device-resident state of one ``generate()`` call's token selection
+    (``select_token``); every tensor lives on ``input_ids``' device.
+
+    * ``seen`` int32 [B, ceil(V/32)]: bitmap (uint32 words) of each row's
+      history: all prompt columns, padding included, plus every emitted
+      token, pads included -- what ``RepetitionPenaltyLogitsProcessor`` sees;
+    * ``step`` int32 [B]: selections made so far; ``unfinished`` int32 [B];
+      ``finish_len`` int32 [B] (``n_steps`` until the row emits EOS);
+    * ``scores`` fp32 [B]; ``out`` int64 [B, n_steps];
+    * ``nxt`` / ``cur`` int64 [B]: the token to embed next and its position
+      ``lens + step`` -- the decode step's static inputs;
+    * ``u`` fp32 [n_steps, B]: the uniforms of a sampling run.
+
+    The scalars mirror ``GPTForGeneration._processors``: ``min_len`` (with an
+    ``eos``), ``penalty``, ``forced_bos`` at step 0, ``forced_eos`` at step
+    ``max_len - 1`` (``max_len`` defaults to ``n_steps``)."""
+
+    def __init__(self, input_ids, lens, vocab, n_steps, greedy=True, temperature=1.0, top_k=0,
+                 top_p=1.0, eos=None, pad=0, min_len=0, penalty=1.0, forced_bos=None,
+                 forced_eos=None, max_len=None, u=None):
+        dev = input_ids.device
+        B = input_ids.shape[0]
+        if not 0 <= pad < vocab:
+            raise ValueError("pad token %d outside the vocabulary" % pad)
+        for t in (eos, forced_bos, forced_eos):
+            if t is not None and not 0 <= t < vocab:
+                raise ValueError("token %d outside the vocabulary" % t)
+        if not greedy and (u is None or tuple(u.shape) != (n_steps, B)):
+            raise ValueError("sampling needs uniforms u [n_steps, B]")
+        self.vocab, self.n_steps, self.greedy = vocab, n_steps, bool(greedy)
+        self.temperature = 1.0 if temperature in (None, 0.0) else float(temperature)
+        self.top_k = int(top_k or 0)
+        self.top_p = float(1.0 if top_p is None else top_p)
+        self.eos, self.pad = eos, pad
+        self.min_len = int(min_len or 0) if eos is not None else 0
+        self.penalty = float(penalty or 1.0)
+        # the kernel's divide: torch's GPU `x / python_float` multiplies by the fp32 reciprocal
+        self.inv_penalty = float(torch.tensor(1.0) / torch.tensor(self.penalty))
+        self.forced_bos, self.forced_eos = forced_bos, forced_eos
+        self.max_len = n_steps if max_len is None else int(max_len)
+        self.u = None if u is None else u.to(dev, torch.float32).contiguous()
+        self.lens = lens.to(dev, torch.long).contiguous()
+        self.seen = _pack_seen(input_ids, vocab)
+        self.step = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.unfinished = torch.ones(B, dtype=torch.int32, device=dev)
+        self.finish_len = torch.full((B,), n_steps, dtype=torch.int32, device=dev)
+        self.scores = torch.zeros(B, dtype=torch.float32, device=dev)
+        self.out = torch.full((B, n_steps), pad, dtype=torch.long, device=dev)
+        self.nxt = torch.zeros(B, dtype=torch.long, device=dev)
+        self.cur = self.lens.clone()
+
+
+def processed_logits(logits, state):
+    """The logits after the processors, as the selection sees them (PyTorch
+    formula; does not change ``state``)."""
+    st = state
+    x = logits.float().clone()
+    step = st.step.long()
+    if st.min_len and st.eos is not None:
+        x[:, st.eos] = torch.where(step < st.min_len, torch.full_like(x[:, 0], -1e9),
+                                   x[:, st.eos])
+    if st.penalty != 1.0:
+        seen = unpack_seen(st.seen, st.vocab)
+        x = torch.where(seen, torch.where(x < 0, x * st.penalty, x / st.penalty), x)
+    for tok, at in ((st.forced_bos, 0), (st.forced_eos, st.max_len - 1)):
+        if tok is not None:
+            forced = torch.full_like(x, -1e9)
+            forced[:, tok] = 0
+            x = torch.where((step == at)[:, None], forced, x)
+    return x
+
+
+def select_token(logits, state):
+    """One step of token selection on the device: the logits processors, the
+    pick (greedy, or top-k / top-p sampling with ``state.u[step]``) and the
+    loop's bookkeeping, all from and into ``state`` (``SelectState``); nothing
+    is read back to the host, so the call can be captured into a HIP graph
+    behind the decode step.  ``logits`` [B, V] fp32 is not written.
+
+    Per row, with ``unf = unfinished``: ``tok = pick if unf else pad``;
+    ``scores += x'[pick] - logsumexp(x')`` if ``unf``; ``out[:, step] = tok``;
+    ``seen`` gains ``tok``; an unfinished row that emits EOS clears
+    ``unfinished`` and sets ``finish_len = step + 1``; ``nxt = tok``,
+    ``cur = lens + step``, ``step += 1``.  A call at ``step >= n_steps`` does
+    nothing.  Returns ``state.nxt``.
+
+    GPU tensors run ``select_kernel`` (a missing extension raises); CPU
+    tensors take the PyTorch formula with the same semantics."""
+    st = state
+    if logits.dim() != 2 or logits.shape[1] != st.vocab:
+        raise ValueError("select_token expects [B, %d] logits" % st.vocab)
+    B, V = logits.shape
+    if logits.is_cuda:
+        if logits.dtype != torch.float32 or logits.stride(1) != 1:
+            logits = logits.float().contiguous()
+        none = lambda t: -1 if t is None else int(t)  # noqa: E731
+        rc = _lib.kernels().select(
+            logits.data_ptr(), logits.stride(0), B, V, 0 if st.greedy else 1,
+            1.0 / st.temperature, st.top_k, st.top_p, _lib.ptr(st.u), st.n_steps, none(st.eos),
+            st.pad, st.min_len, st.penalty, st.inv_penalty, none(st.forced_bos),
+            none(st.forced_eos), st.max_len - 1, st.seen.data_ptr(), st.seen.shape[1],
+            st.step.data_ptr(),
+            st.unfinished.data_ptr(), st.finish_len.data_ptr(), st.scores.data_ptr(),
+            st.out.data_ptr(), st.nxt.data_ptr(), st.cur.data_ptr(), st.lens.data_ptr(),
+            _lib.stream())
+        if rc != 0:
+            raise RuntimeError("token selection launch failed ({})".format(rc))
+        _lib.maybe_sync()
+        return st.nxt
+    step = st.step.long()
+    live = step < st.n_steps
+    if not bool(live.any()):
+        return st.nxt
+    x = processed_logits(logits, st)
+    lse = torch.logsumexp(x, -1)
+    if st.greedy:
+        pick = torch.argmax(x, -1)
+    else:
+        from ..models.language_model.gpt.generation import top_k_filter, top_p_filter
+        probs = torch.softmax(x / st.temperature if st.temperature != 1.0 else x, -1)
+        if st.top_k:
+            probs = top_k_filter(probs, st.top_k)
+        if st.top_p < 1.0:
+            probs = top_p_filter(probs, st.top_p)
+        # inverse CDF in index order: the first kept token whose running mass passes u * total
+        c = torch.cumsum(probs, -1)
+        u = st.u[step.clamp(max=st.n_steps - 1), torch.arange(B)]
+        pick = (c <= (u * c[:, -1])[:, None]).sum(-1)
+        last = (V - 1) - (probs > 0).flip(-1).long().argmax(-1)
+        pick = torch.minimum(pick, last)
+    unf = (st.unfinished != 0) & live
+    tok = torch.where(unf, pick, torch.full_like(pick, st.pad))
+    st.scores += torch.where(unf, x.gather(1, pick[:, None]).squeeze(1) - lse,
+                             torch.zeros_like(lse))
+    rows = torch.arange(B)[live]
+    st.out[rows, step[live]] = tok[live]
+    word = st.seen[rows, tok[live] >> 5].long() | \
+        (torch.ones_like(rows) << (tok[live] & 31))
+    st.seen[rows, tok[live] >> 5] = torch.where(word >= 2 ** 31, word - 2 ** 32,
+                                                word).to(torch.int32)
+    if st.eos is not None:
+        fin = unf & (tok == st.eos)
+        st.finish_len.copy_(torch.where(fin, (step + 1).int(), st.finish_len))
+        st.unfinished.copy_(torch.where(fin, torch.zeros_like(st.unfinished), st.unfinished))
+    st.nxt.copy_(torch.where(live, tok, st.nxt))
+    st.cur.copy_(torch.where(live, st.lens + step, st.cur))
+    st.step += live.int()
+    return st.nxt

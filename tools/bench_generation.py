@@ -5,12 +5,15 @@ epilogues).  Random-init weights, bf16.
     python tools/bench_generation.py [--model gpt3-1.3B] [--batch 1 8 16] [--tokens 64]
                                      [--strategy beam_search --num-beams 4]
                                      [--weight-quant int8 [--repeat 2]]
+                                     [--device-loop [--repeat 3]]
 
 One JSON line per (batch, fused): ms/token, tokens/s and the effective weight
 stream rate (parameter bytes / ms per token).  ``--weight-quant int8`` adds the
 weight-only int8 decode path to every series, alternating with the 16-bit
 one in the same process; ``--repeat`` runs each series that many times (the
-spread of the 16-bit repeats is the yardstick for any difference)."""
+spread of the 16-bit repeats is the yardstick for any difference).
+``--device-loop`` adds every fused series once more with the token selection
+on the device (``Generation.device_loop``), alternating in the same way."""
 import argparse
 import json
 import os
@@ -36,6 +39,8 @@ def main():
     ap.add_argument("--num-beams", type=int, default=1)
     ap.add_argument("--weight-quant", default=None, choices=["int8"],
                     help="also run the fused decode on weight-only int8 copies")
+    ap.add_argument("--device-loop", action="store_true",
+                    help="also run every fused series with Generation.device_loop")
     ap.add_argument("--repeat", type=int, default=1)
     args = ap.parse_args()
     from fleetx_amd.models.language_model.gpt.model import GPTConfig, GPTForPretraining
@@ -48,13 +53,16 @@ def main():
     nbytes = sum(p.numel() * p.element_size() for p in model.parameters())
     for B in args.batch:
         prompt = torch.randint(0, 50304, (B, args.prompt), device="cuda")
-        series = [(f, None) for f in ((True,) if args.fused_only else (False, True))]
+        series = [(f, None, False) for f in ((True,) if args.fused_only else (False, True))]
         if args.weight_quant:
-            series.append((True, args.weight_quant))
-        for fused, wq in series * args.repeat:
+            series.append((True, args.weight_quant, False))
+        if args.device_loop and args.strategy != "beam_search":
+            series += [(f, wq, True) for f, wq, _ in series if f]
+        for fused, wq, dloop in series * args.repeat:
             gen = GPTForGeneration(model, {"max_dec_len": args.tokens, "fused_decode": fused,
                                            "decode_strategy": args.strategy,
-                                           "num_beams": args.num_beams, "weight_quant": wq})
+                                           "num_beams": args.num_beams, "weight_quant": wq,
+                                           "device_loop": dloop})
             gen.generate(prompt, max_length=8)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -71,6 +79,7 @@ def main():
             print(json.dumps({"model": args.model, "batch": B, "strategy": args.strategy,
                               "num_beams": args.num_beams if args.strategy == "beam_search" else 1,
                               "fused_decode": fused, "weight_quant": wq,
+                              "device_loop": dloop,
                               "persistent_layers": persistent,
                               "ms_per_token": round(ms, 3),
                               "tokens_per_s": round(B * 1e3 / ms, 1),
