@@ -299,6 +299,17 @@ PYBIND11_MODULE(_kernels, m) {
                              P(y), ldy, P(kc), P(vc), reinterpret_cast<const long*>(pos), heads,
                              head_dim, maxlen, CP(ln_w), CP(ln_b), ln_eps, S(st));
   });
+  // the same with packed int4 weights (ldw in bytes) and one fp32 scale per k-group of 256
+  // and output row, [K / 256, N] (decode_gemv_w4.hip)
+  m.def("decode_gemv_w4", [](int dt, int epi, int M, int N, int K, ptr x, long ldx, ptr wq, long ldw,
+                             ptr wscale, ptr bias, ptr res, long ldres, ptr y, long ldy, ptr kc,
+                             ptr vc, ptr pos, int heads, int head_dim, int maxlen, ptr ln_w,
+                             ptr ln_b, float ln_eps, ptr st) {
+    return fx_decode_gemv_w4(dt, epi, M, N, K, CP(x), ldx, reinterpret_cast<const uint8_t*>(wq), ldw,
+                             reinterpret_cast<const float*>(wscale), CP(bias), CP(res), ldres,
+                             P(y), ldy, P(kc), P(vc), reinterpret_cast<const long*>(pos), heads,
+                             head_dim, maxlen, CP(ln_w), CP(ln_b), ln_eps, S(st));
+  });
   // CU-masked stream (streams.hip): returns (stream handle, CUs selected)
   m.def("cumask_stream_create", [](int ncu) {
     int got = 0;

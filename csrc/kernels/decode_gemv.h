@@ -3,10 +3,12 @@
 // and an optional LayerNorm of x fused as a prologue.  This header holds the
 // kernel, the launch ladder and the host entry once; a weight format is a
 // small policy type W (decode_gemv.hip: 16-bit, decode_gemv_w8.hip: int8 with
-// a scale per output row) that supplies
+// a scale per output row, decode_gemv_w4.hip: int4 with a scale per k-group
+// and output row) that supplies
 //   elt, reg      weight element type and the 16-byte per-lane register type
+//   PACK          weights per elt (1; int4: 2 per byte)
 //   Ptrs          the weight pointer block of the argument struct: w (const
-//                 elt*), with SCALED scale (const float*), and valid(), the
+//                 elt*), with SCALED or GROUPED scale (const float*), and valid(), the
 //                 host check of the block
 //   CHUNK         k elements per chunk: every lane loads 32 contiguous bytes
 //                 (reg[2]) of one W row per chunk, so CHUNK / 4 k per lane and
@@ -14,6 +16,10 @@
 //   mma_batch<T, U>  the MFMAs of U loaded chunks: registers -> the A operand
 //                 of each of a chunk's k-steps (as loaded, or converted)
 //   SCALED        accumulator times Ptrs::scale[n] before the bias
+//   GROUPED       one chunk is one scale group: Ptrs::scale is [K / CHUNK, N],
+//                 the lane's four scales of a chunk are loaded with the chunk's
+//                 weights and mma_batch takes them as a fourth argument (it
+//                 sums the chunk from zero and adds sum * scale to acc)
 //   U, U_MIN      chunks per load batch: U, or U_MIN when a wave's K range is
 //                 no multiple of U chunks
 //   STEADY_LOOP   which of the kernel's two K-loop schedules runs
@@ -69,12 +75,39 @@ __device__ __forceinline__ floatx4 mma16(const short8& a, const short8& b, const
                                                   __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
 }
 
+// int8 weight operands (W8; W4 after it has spread its nibbles into bytes)
+// two int8 (bytes B0 and B1 of v) -> two packed 16-bit floats.  Every integer
+// in [-128, 127] is exact in bf16 (8 significant bits) and fp16.
+template <typename T, int B0, int B1>
+__device__ __forceinline__ uint32_t cvt2(uint32_t v) {
+  const float f0 = (float)(int8_t)(v >> (8 * B0));
+  const float f1 = (float)(int8_t)(v >> (8 * B1));
+  if constexpr (std::is_same<T, bf16>::value) {
+    // an exact small integer: the low 16 fp32 bits are zero, truncation is exact
+    return __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, f1),
+                                 __builtin_bit_cast(uint32_t, f0), 0x07060302u);
+  } else {
+    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(f0, f1));
+  }
+}
+// eight int8 (two dwords) -> one MFMA operand, element order = byte order
+template <typename T>
+__device__ __forceinline__ short8 cvt8(uint32_t lo, uint32_t hi) {
+  uint4 o;
+  o.x = cvt2<T, 0, 1>(lo);
+  o.y = cvt2<T, 2, 3>(lo);
+  o.z = cvt2<T, 0, 1>(hi);
+  o.w = cvt2<T, 2, 3>(hi);
+  return __builtin_bit_cast(short8, o);
+}
+
 template <typename W, int U>
 __device__ __forceinline__ void load_w(typename W::reg (&wv)[U][2], const typename W::elt* wp,
                                        int c) {
 #pragma unroll
   for (int u = 0; u < U; ++u) {
-    const typename W::reg* p = reinterpret_cast<const typename W::reg*>(wp + (c + u) * W::CHUNK);
+    const typename W::reg* p =
+        reinterpret_cast<const typename W::reg*>(wp + (c + u) * (W::CHUNK / W::PACK));
     wv[u][0] = __builtin_nontemporal_load(p);
     wv[u][1] = __builtin_nontemporal_load(p + 1);
   }
@@ -104,6 +137,39 @@ __device__ __forceinline__ void load_batch(typename W::reg (&wv)[U][2],
   load_w<W, U>(wv, wp, c);
   load_x<W, U, XL>(xv, xp, c);
 }
+
+// GROUPED: the four scales scale[chunk, n] of the lane's accumulator columns
+// (nj: their clamped column numbers).  Four dword loads: a row of scales is N
+// floats, so no alignment beyond 4 bytes holds.
+template <typename W, int U>
+__device__ __forceinline__ void load_s(floatx4 (&sv)[U], const float* sp, int N,
+                                       const int (&nj)[4], int c) {
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const float* p = sp + (long)(c + u) * N;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sv[u][j] = p[nj[j]];
+  }
+}
+
+// The kernel's load and MFMA steps; with W::GROUPED they carry the chunk scales
+// (sa / sb beside wa / wb).  Macros, not functions: a further level of inlining
+// around these calls moves the code generation of every instantiation.
+#define GV_LOAD_W(w, s, c)                                        \
+  do {                                                            \
+    load_w<W, U>(w, wp, c);                                       \
+    if constexpr (W::GROUPED) load_s<W, U>(s, sp, a.N, nj, c);    \
+  } while (0)
+#define GV_LOAD_BATCH(XL, w, x, s, c)                             \
+  do {                                                            \
+    load_batch<W, U, XL>(w, x, wp, xp, c);                        \
+    if constexpr (W::GROUPED) load_s<W, U>(s, sp, a.N, nj, c);    \
+  } while (0)
+#define GV_MMA(w, x, s)                                           \
+  do {                                                            \
+    if constexpr (W::GROUPED) W::template mma_batch<T, U>(acc, w, x, s); \
+    else W::template mma_batch<T, U>(acc, w, x);                  \
+  } while (0)
 
 // Fused LayerNorm prologue: rows m < M of x [M, K] normalised (fp32 math,
 // shifted one-pass moments: the row's first element is subtracted before the
@@ -220,7 +286,8 @@ __global__ __launch_bounds__(64 * GV_KS) void gemv_kernel(GemvArgs<W> a) {
   const int kw = a.K / GV_KS;  // multiple of CHUNK * U (host check)
   const int kb = w * kw;
   const int nrow = min(n0 + (r % RW), a.N - 1);
-  const typename W::elt* wp = a.wp.w + (long)nrow * a.ldw + kb + W::CHUNK / 4 * g;
+  const typename W::elt* wp =
+      a.wp.w + (long)nrow * a.ldw + kb / W::PACK + W::CHUNK / 4 / W::PACK * g;
   // x rows >= M read row M-1 (no per-load select: their D rows are never stored)
   // LN rows in LDS are K + 8 elements apart: the 16 lanes' rows fall on different banks
   const uint16_t* xp = LN ? xs_dyn + (long)min(r, a.M - 1) * (a.K + 8) + kb + W::CHUNK / 4 * g
@@ -236,6 +303,16 @@ __global__ __launch_bounds__(64 * GV_KS) void gemv_kernel(GemvArgs<W> a) {
   // profiles/decode_gemv_shared/README.md before merging or moving them.
   typename W::reg wa[U][2], wb[U][2];
   short8 xa[U][W::CHUNK / 32], xb[U][W::CHUNK / 32];
+  // GROUPED: chunk scales of the two register sets, the scale rows of this
+  // wave's K range and the lane's accumulator columns D[n = 4g + j]
+  floatx4 sa[W::GROUPED ? U : 1], sb[W::GROUPED ? U : 1];
+  const float* sp = nullptr;
+  int nj[4];
+  if constexpr (W::GROUPED) {
+    sp = a.wp.scale + (long)(kb / W::CHUNK) * a.N;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) nj[j] = min(n0 + (4 * g + j) % RW, a.N - 1);
+  }
   if constexpr (W::STEADY_LOOP) {
     // Branch-free steady loop with peeled head and tail: no branch around the
     // loads, so the compiler counts vmcnt exactly and batch c+1 really stays in
@@ -244,55 +321,55 @@ __global__ __launch_bounds__(64 * GV_KS) void gemv_kernel(GemvArgs<W> a) {
     int c = 0;
     bool done = false;
     if constexpr (LN) {
-      load_w<W, U>(wa, wp, 0);
-      if (U < nch) load_w<W, U>(wb, wp, U);
+      GV_LOAD_W(wa, sa, 0);
+      if (U < nch) GV_LOAD_W(wb, sb, U);
       ln_prologue<W, T, 64 * GV_KS, LNR>(a, xs_dyn, red);
       load_x<W, U, true>(xa, xp, 0);
       if (U < nch) {
         load_x<W, U, true>(xb, xp, U);
-        W::template mma_batch<T, U>(acc, wa, xa);
-        if (2 * U < nch) load_batch<W, U, LN>(wa, xa, wp, xp, 2 * U);
+        GV_MMA(wa, xa, sa);
+        if (2 * U < nch) GV_LOAD_BATCH(LN, wa, xa, sa, 2 * U);
         else done = true;
-        W::template mma_batch<T, U>(acc, wb, xb);
+        GV_MMA(wb, xb, sb);
         c = 2 * U;
       }
     } else {
-      load_batch<W, U, false>(wa, xa, wp, xp, 0);
+      GV_LOAD_BATCH(false, wa, xa, sa, 0);
     }
     if (!done) {
       // set a holds batch c
       for (; c + 2 * U < nch; c += 2 * U) {
-        load_batch<W, U, LN>(wb, xb, wp, xp, c + U);
-        W::template mma_batch<T, U>(acc, wa, xa);
-        load_batch<W, U, LN>(wa, xa, wp, xp, c + 2 * U);
-        W::template mma_batch<T, U>(acc, wb, xb);
+        GV_LOAD_BATCH(LN, wb, xb, sb, c + U);
+        GV_MMA(wa, xa, sa);
+        GV_LOAD_BATCH(LN, wa, xa, sa, c + 2 * U);
+        GV_MMA(wb, xb, sb);
       }
       if (c + U < nch) {
-        load_batch<W, U, LN>(wb, xb, wp, xp, c + U);
-        W::template mma_batch<T, U>(acc, wa, xa);
-        W::template mma_batch<T, U>(acc, wb, xb);
+        GV_LOAD_BATCH(LN, wb, xb, sb, c + U);
+        GV_MMA(wa, xa, sa);
+        GV_MMA(wb, xb, sb);
       } else {
-        W::template mma_batch<T, U>(acc, wa, xa);
+        GV_MMA(wa, xa, sa);
       }
     }
   } else {
     // Guarded loop with break: every load sits behind a bounds test.
     if constexpr (LN) {
-      load_w<W, U>(wa, wp, 0);
-      if (U < nch) load_w<W, U>(wb, wp, U);
+      GV_LOAD_W(wa, sa, 0);
+      if (U < nch) GV_LOAD_W(wb, sb, U);
       ln_prologue<W, T, 64 * GV_KS, LNR>(a, xs_dyn, red);
       load_x<W, U, true>(xa, xp, 0);
       if (U < nch) load_x<W, U, true>(xb, xp, U);
     } else {
-      load_batch<W, U, false>(wa, xa, wp, xp, 0);
+      GV_LOAD_BATCH(false, wa, xa, sa, 0);
     }
     for (int c = 0; c < nch; c += 2 * U) {
       if (!LN || c > 0)
-        if (c + U < nch) load_batch<W, U, LN>(wb, xb, wp, xp, c + U);
-      W::template mma_batch<T, U>(acc, wa, xa);
+        if (c + U < nch) GV_LOAD_BATCH(LN, wb, xb, sb, c + U);
+      GV_MMA(wa, xa, sa);
       if (c + U >= nch) break;
-      if (c + 2 * U < nch) load_batch<W, U, LN>(wa, xa, wp, xp, c + 2 * U);
-      W::template mma_batch<T, U>(acc, wb, xb);
+      if (c + 2 * U < nch) GV_LOAD_BATCH(LN, wa, xa, sa, c + 2 * U);
+      GV_MMA(wb, xb, sb);
     }
   }
   if constexpr (LN) __syncthreads();  // red[] doubled as the LN scratch
@@ -420,7 +497,8 @@ int gemv_entry(int dt, int epi, int M, int N, int K, const void* x, long ldx,
   if ((pin_ks == 4 || pin_ks == 8) && K % (W::CHUNK * W::U_MIN * pin_ks) == 0) ks = pin_ks;
   // With the default ks a wave's K range is always a multiple of U chunks; only
   // the int8 FLEETX_GEMV_W8_KS=8 pin at K an odd multiple of 1024 leaves an odd
-  // number of chunks and takes U_MIN (for W16, U_MIN == U)
+  // number of chunks and takes U_MIN (for W16, U_MIN == U); int4 has odd counts
+  // at the default ks too (K = 1024: one chunk per wave)
   int u = (K / (W::CHUNK * ks)) % W::U == 0 ? W::U : W::U_MIN;
   if (pin_u == W::U_MIN) u = W::U_MIN;
   int rw = N <= 2048 ? 8 : 16;
@@ -437,5 +515,9 @@ int gemv_entry(int dt, int epi, int M, int N, int K, const void* x, long ldx,
   else launch_epi<W, f16>(a, epi, ln, u, ks, rw, s);
   return (N + rw - 1) / rw;
 }
+
+#undef GV_LOAD_W
+#undef GV_LOAD_BATCH
+#undef GV_MMA
 
 }  // namespace

@@ -30,8 +30,8 @@ struct W16 {
     const uint16_t* w;
     bool valid() const { return (uintptr_t)w % 16 == 0; }
   };
-  static constexpr int CHUNK = 64;
-  static constexpr bool SCALED = false;
+  static constexpr int CHUNK = 64, PACK = 1;
+  static constexpr bool SCALED = false, GROUPED = false;
   static constexpr int U = 4, U_MIN = 4;
   static constexpr bool STEADY_LOOP = false;
   static constexpr const char* PIN_KS = "FLEETX_GEMV_KS";

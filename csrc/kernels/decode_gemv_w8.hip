@@ -7,7 +7,8 @@
 // file is the int8 weight operand, converted in registers:
 //  * per 128-k chunk every lane loads 32 contiguous bytes of one q row and the
 //    matching 32 x elements, for the chunk's four MFMA k-steps;
-//  * each int8 is sign-extended and converted to fp32, then packed to the
+//  * each int8 is sign-extended and converted to fp32 (cvt8 in decode_gemv.h,
+//    shared with the int4 operand), then packed to the
 //    activation dtype (bf16: the upper half of the fp32, exact for |q| <= 127;
 //    fp16: cvt_pkrtz, exact too) right before its MFMA -- ~1.5 VALU lane-ops
 //    per element;
@@ -23,31 +24,6 @@
 
 namespace {
 
-// two int8 (bytes B0 and B1 of v) -> two packed 16-bit floats.  Every integer
-// in [-128, 127] is exact in bf16 (8 significant bits) and fp16.
-template <typename T, int B0, int B1>
-__device__ __forceinline__ uint32_t cvt2(uint32_t v) {
-  const float f0 = (float)(int8_t)(v >> (8 * B0));
-  const float f1 = (float)(int8_t)(v >> (8 * B1));
-  if constexpr (std::is_same<T, bf16>::value) {
-    // an exact small integer: the low 16 fp32 bits are zero, truncation is exact
-    return __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, f1),
-                                 __builtin_bit_cast(uint32_t, f0), 0x07060302u);
-  } else {
-    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(f0, f1));
-  }
-}
-// eight int8 (two dwords) -> one MFMA operand, element order = byte order
-template <typename T>
-__device__ __forceinline__ short8 cvt8(uint32_t lo, uint32_t hi) {
-  uint4 o;
-  o.x = cvt2<T, 0, 1>(lo);
-  o.y = cvt2<T, 2, 3>(lo);
-  o.z = cvt2<T, 0, 1>(hi);
-  o.w = cvt2<T, 2, 3>(hi);
-  return __builtin_bit_cast(short8, o);
-}
-
 struct W8 {
   typedef int8_t elt;
   typedef uintx4 reg;
@@ -56,8 +32,8 @@ struct W8 {
     const float* scale;
     bool valid() const { return (uintptr_t)w % 16 == 0 && scale != nullptr; }
   };
-  static constexpr int CHUNK = 128;
-  static constexpr bool SCALED = true;
+  static constexpr int CHUNK = 128, PACK = 1;
+  static constexpr bool SCALED = true, GROUPED = false;
   static constexpr int U = 2, U_MIN = 1;
   static constexpr bool STEADY_LOOP = true;
   static constexpr const char* PIN_KS = "FLEETX_GEMV_W8_KS";

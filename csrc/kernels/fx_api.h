@@ -112,6 +112,9 @@ int fx_decode_gemv(int, int, int, int, int, const void*, long, const void*, long
 int fx_decode_gemv_w8(int, int, int, int, int, const void*, long, const int8_t*, long, const float*,
                       const void*, const void*, long, void*, long, void*, void*, const long*, int,
                       int, int, const void*, const void*, float, hipStream_t);
+int fx_decode_gemv_w4(int, int, int, int, int, const void*, long, const uint8_t*, long, const float*,
+                      const void*, const void*, long, void*, long, void*, void*, const long*, int,
+                      int, int, const void*, const void*, float, hipStream_t);
 hipStream_t fx_cumask_stream_create(int, int*);
 int fx_stream_destroy(hipStream_t);
 int fx_comm_max_world();

@@ -263,11 +263,23 @@ def _fusable(layer):
 _LN_FUSE = os.environ.get("FLEETX_DECODE_LN_FUSE", "1") == "1"
 
 
+# weight_quant value -> (quantiser in ops, its decode GEMV in ops.gemm, k-group
+# size); a quantised copy is stored as (GEMV name, q, scale), so the format
+# travels with it
+_WEIGHT_QUANT = {"int8": ("quantize_weight_int8", "decode_linear_w8", 1),
+                 "int4_g256": ("quantize_weight_int4", "decode_linear_w4", 256)}
+
+
+def _qlin(G, x, q8, *args, **kw):
+    """The decode GEMV of the quantised copy ``q8 = (GEMV name, q, scale)``."""
+    return getattr(G, q8[0])(x, q8[1], q8[2], *args, **kw)
+
+
 def _dlin(G, x, lin, epi, q8, **kw):
-    """One decode GEMV of ``lin``: on its int8 copy ``q8 = (q, scale)`` where
-    there is one and the int8 kernel covers the call, else on the 16-bit weight."""
+    """One decode GEMV of ``lin``: on its quantised copy ``q8`` where there is
+    one and its kernel covers the call, else on the 16-bit weight."""
     if q8 is not None:
-        y = G.decode_linear_w8(x, q8[0], q8[1], lin.bias, epi, **kw)
+        y = _qlin(G, x, q8, lin.bias, epi, **kw)
         if y is not None:
             return y
     return G.decode_linear(x, lin.weight, lin.bias, epi, **kw)
@@ -281,8 +293,8 @@ def _layer_decode_fused(layer, x, cache, li, pos, lens_after, w8=None):
     bias + residual].  The LayerNorms run as GEMV prologues (each block
     normalises the few rows into LDS); shapes the fused prologue does not
     cover fall back to a separate LayerNorm launch.  Returns None when a GEMV
-    does not cover the shape (batch > 16).  ``w8`` (``weight_quant: int8``) maps
-    ``qkv_proj`` / ``out_proj`` / ``fc1`` / ``fc2`` to this layer's int8 copies."""
+    does not cover the shape (batch > 16).  ``w8`` (``weight_quant``) maps
+    ``qkv_proj`` / ``out_proj`` / ``fc1`` / ``fc2`` to this layer's quantised copies."""
     from ....ops import gemm as G
     attn, mlp = layer.attn, layer.mlp
     w8 = w8 or {}
@@ -412,11 +424,12 @@ class GPTForGeneration(torch.nn.Module):
         self.fused_decode = bool(c.get("fused_decode", True))
         self.length_penalty = c.get("length_penalty", 0.0)
         self.early_stopping = bool(c.get("early_stopping", False))
-        # weight-only int8 copies of the decode GEMV weights (None: 16-bit weights)
+        # weight-only int8 / int4 copies of the decode GEMV weights (None: 16-bit weights)
         self.weight_quant = c.get("weight_quant")
-        if self.weight_quant not in (None, "int8"):
-            raise ValueError("weight_quant must be None or 'int8' (got %r)" % (self.weight_quant,))
-        self._w8 = None        # {"layers": [{name: (q, scale)}], "head": (q, scale)}
+        if self.weight_quant is not None and self.weight_quant not in _WEIGHT_QUANT:
+            raise ValueError("weight_quant must be None, %s (got %r)"
+                             % (" or ".join(repr(k) for k in _WEIGHT_QUANT), self.weight_quant))
+        self._w8 = None        # {"layers": [{name: (GEMV name, q, scale)}], "head": (...)}
         self._w8_src = []      # (weight, _version, data_ptr) of every quantised weight
         self._w8_warned = False
         # token selection on the device, one graph replay per token (sampling / greedy)
@@ -449,7 +462,7 @@ class GPTForGeneration(torch.nn.Module):
             procs.append(ForcedEOSTokenLogitsProcessor(max_len, self.forced_eos_token_id))
         return procs
 
-    # ---- weight-only int8 decode (weight_quant: int8)
+    # ---- weight-only quantised decode (weight_quant: int8 / int4_g256)
     def _w8_sources(self):
         """The weights the decode step streams: four per fusable layer and the
         tied embedding table (as the LM head)."""
@@ -462,18 +475,20 @@ class GPTForGeneration(torch.nn.Module):
         return per_layer, self.gpt.embeddings.word_embeddings.weight
 
     def requantize(self):
-        """(Re)build the int8 copies from the current 16-bit weights.  The
+        """(Re)build the quantised copies from the current 16-bit weights.  The
         16-bit weights stay resident (prefill and the embedding lookup use
-        them): the int8 path buys decode bandwidth, not memory.  Returns True
-        when the int8 path is active; on CPU or under tensor parallel the key
-        is accepted and ignored with one warning (those paths do not stream
-        weights through the decode GEMV)."""
+        them): the quantised path buys decode bandwidth, not memory.  Returns
+        True when the quantised path is active; on CPU or under tensor parallel
+        the key is accepted and ignored with one warning (those paths do not
+        stream weights through the decode GEMV).  A weight the format cannot
+        hold (int4: K no multiple of the group size) keeps no copy and decodes
+        on its 16-bit weight."""
         if self.weight_quant is None:
             return False
         head = self.gpt.embeddings.word_embeddings.weight
         if not head.is_cuda or topo.mp_world_size() != 1 or not self.fused_decode:
             if not self._w8_warned:
-                warnings.warn("weight_quant=%r is ignored: the int8 decode path needs a GPU, "
+                warnings.warn("weight_quant=%r is ignored: the quantised decode path needs a GPU, "
                               "fused_decode and no tensor parallelism" % (self.weight_quant,))
                 self._w8_warned = True
             self._w8, self._w8_src = None, []
@@ -481,9 +496,13 @@ class GPTForGeneration(torch.nn.Module):
         per_layer, head = self._w8_sources()
         src = []
 
+        quantiser, gemv, group = _WEIGHT_QUANT[self.weight_quant]
+
         def quant(w):
             src.append((w, w._version, w.data_ptr()))
-            return ops.quantize_weight_int8(w)
+            if w.shape[1] % group:
+                return None
+            return (gemv,) + getattr(ops, quantiser)(w)
         with torch.no_grad():
             self._w8 = {"layers": [{k: quant(w) for k, w in d.items()} for d in per_layer],
                         "head": quant(head)}
@@ -535,14 +554,14 @@ class GPTForGeneration(torch.nn.Module):
         return self._logits(x[:, 0], self._w8["head"] if self._w8 is not None else None)
 
     def _logits(self, h, q8=None):
-        """``q8``: the int8 copy of the tied table (decode steps; the prefill's
+        """``q8``: the quantised copy of the tied table (decode steps; the prefill's
         last-token logits use the 16-bit table like the rest of the prefill)."""
         w = self.gpt.embeddings.word_embeddings.weight
         logits = None
         if self.fused_decode and topo.mp_world_size() == 1:
             from ....ops import gemm as G
             if q8 is not None:
-                logits = G.decode_linear_w8(h.contiguous(), q8[0], q8[1])
+                logits = _qlin(G, h.contiguous(), q8)
             if logits is None:
                 logits = G.decode_linear(h.contiguous(), w)
         if logits is None:

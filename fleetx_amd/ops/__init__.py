@@ -5,6 +5,8 @@ from .attention import (flash_attention, flash_attention_qkvpacked, attention_re
                         decode_attention, beam_decode_attention)
 from .loss_embed import softmax_cross_entropy, embedding  # noqa: F401
 from .quant import fake_quant, quantize_weight_int8, dequantize_weight_int8  # noqa: F401
+from .quant import (quantize_weight_int4, dequantize_weight_int4, pack_int4,  # noqa: F401
+                    unpack_int4)
 from .sampling import fused_sample, select_token, SelectState  # noqa: F401
 from .softmax import (fused_softmax, softmax_mask_fuse,  # noqa: F401
                       softmax_mask_fuse_upper_triangle)

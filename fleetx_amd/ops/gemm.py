@@ -429,29 +429,34 @@ def wgrad_16(dy2, x2):
 
 # ----------------------------------------------------------------------------
 # decode-time skinny GEMM (csrc/kernels/decode_gemv.h: one kernel template over
-# the weight operand -- decode_gemv.hip 16-bit, decode_gemv_w8.hip int8)
+# the weight operand -- decode_gemv.hip 16-bit, decode_gemv_w8.hip int8,
+# decode_gemv_w4.hip int4 with a scale per group of 256 k)
 # ----------------------------------------------------------------------------
 GV_BIAS, GV_GELU, GV_RES, GV_QKV = range(4)
 
 
-def _decode_gemv(x, w, wscale, bias, epi, res, qkv_cache, ln):
+def _decode_gemv(x, w, wscale, bias, epi, res, qkv_cache, ln, int4=False):
     """The body of ``decode_linear`` (``wscale`` None: ``w`` is a 16-bit weight
-    of ``x.dtype``) and ``decode_linear_w8`` (``w`` int8, ``wscale`` fp32 [N]):
-    the checks, the QKV unpacking, the output and the call.  None for a call
-    the kernel does not cover; malformed caches / residual assert."""
+    of ``x.dtype``), ``decode_linear_w8`` (``w`` int8, ``wscale`` fp32 [N]) and
+    ``decode_linear_w4`` (``int4``: ``w`` packed uint8 [N, K / 2], ``wscale``
+    fp32 [K / 256, N]): the checks, the QKV unpacking, the output and the call.
+    None for a call the kernel does not cover; malformed caches / residual
+    assert."""
     if not x.is_cuda or x.dim() != 2 or x.shape[0] < 1 or x.shape[0] > 16 \
             or x.dtype not in (torch.bfloat16, torch.float16):
         return None
     M, K = x.shape
-    wdtype = x.dtype if wscale is None else torch.int8
-    if w.dim() != 2 or w.dtype != wdtype or not w.is_cuda or w.shape[1] != K:
+    wdtype = x.dtype if wscale is None else torch.uint8 if int4 else torch.int8
+    if w.dim() != 2 or w.dtype != wdtype or not w.is_cuda or w.shape[1] * (2 if int4 else 1) != K:
         return None
     N = w.shape[0]
     if w.stride(1) != 1 or x.stride(1) != 1 or K % 1024 or x.stride(0) % 8 \
             or (w.stride(0) * w.element_size()) % 16 or w.data_ptr() % 16 or x.data_ptr() % 16:
         return None
     if wscale is not None and (wscale.dtype != torch.float32 or not wscale.is_cuda
-                               or wscale.numel() != N or not wscale.is_contiguous()):
+                               or (wscale.shape != (K // 256, N) if int4
+                                   else wscale.numel() != N)
+                               or not wscale.is_contiguous()):
         return None
     if bias is not None and (bias.dtype != x.dtype or bias.numel() != N
                              or not bias.is_contiguous()):
@@ -485,6 +490,8 @@ def _decode_gemv(x, w, wscale, bias, epi, res, qkv_cache, ln):
             float(ln[2]) if ln is not None else 0.0, _lib.stream())
     if wscale is None:
         nb = k.decode_gemv(*head, *tail)
+    elif int4:
+        nb = k.decode_gemv_w4(*head, wscale.data_ptr(), *tail)
     else:
         nb = k.decode_gemv_w8(*head, wscale.data_ptr(), *tail)
     if nb == 0:
@@ -521,3 +528,18 @@ def decode_linear_w8(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, qkv_cache=
     if wscale is None:
         return None
     return _decode_gemv(x, wq, wscale, bias, epi, res, qkv_cache, ln)
+
+
+def decode_linear_w4(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, qkv_cache=None, ln=None):
+    """``decode_linear`` with a weight-only int4 weight of group size 256:
+    ``wq`` packed uint8 [N, K / 2] and ``wscale`` fp32 [K / 256, N] from
+    ``ops.quantize_weight_int4``.  The int4 values are converted to ``x.dtype``
+    in registers (exactly), every group of 256 k accumulates in fp32 from zero
+    and enters the accumulator times its scale; the bias and the epilogue
+    follow as in ``decode_linear``.
+
+    Returns the output, or None when the kernel does not cover the call (the
+    caller then uses the 16-bit weight)."""
+    if wscale is None:
+        return None
+    return _decode_gemv(x, wq, wscale, bias, epi, res, qkv_cache, ln, int4=True)

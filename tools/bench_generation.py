@@ -4,13 +4,13 @@ epilogues).  Random-init weights, bf16.
 
     python tools/bench_generation.py [--model gpt3-1.3B] [--batch 1 8 16] [--tokens 64]
                                      [--strategy beam_search --num-beams 4]
-                                     [--weight-quant int8 [--repeat 2]]
+                                     [--weight-quant int8 int4_g256 [--repeat 2]]
                                      [--device-loop [--repeat 3]]
 
 One JSON line per (batch, fused): ms/token, tokens/s and the effective weight
-stream rate (parameter bytes / ms per token).  ``--weight-quant int8`` adds the
-weight-only int8 decode path to every series, alternating with the 16-bit
-one in the same process; ``--repeat`` runs each series that many times (the
+stream rate (parameter bytes / ms per token).  ``--weight-quant int8`` / ``int4_g256`` (or
+both) adds the weight-only quantised decode paths to every series, alternating
+with the 16-bit one in the same process; ``--repeat`` runs each series that many times (the
 spread of the 16-bit repeats is the yardstick for any difference).
 ``--device-loop`` adds every fused series once more with the token selection
 on the device (``Generation.device_loop``), alternating in the same way."""
@@ -37,8 +37,8 @@ def main():
     ap.add_argument("--strategy", default="greedy_search",
                     choices=["greedy_search", "sampling", "beam_search"])
     ap.add_argument("--num-beams", type=int, default=1)
-    ap.add_argument("--weight-quant", default=None, choices=["int8"],
-                    help="also run the fused decode on weight-only int8 copies")
+    ap.add_argument("--weight-quant", default=[], nargs="+", choices=["int8", "int4_g256"],
+                    help="also run the fused decode on weight-only int8 / int4 copies")
     ap.add_argument("--device-loop", action="store_true",
                     help="also run every fused series with Generation.device_loop")
     ap.add_argument("--repeat", type=int, default=1)
@@ -54,8 +54,7 @@ def main():
     for B in args.batch:
         prompt = torch.randint(0, 50304, (B, args.prompt), device="cuda")
         series = [(f, None, False) for f in ((True,) if args.fused_only else (False, True))]
-        if args.weight_quant:
-            series.append((True, args.weight_quant, False))
+        series += [(True, wq, False) for wq in args.weight_quant]
         if args.device_loop and args.strategy != "beam_search":
             series += [(f, wq, True) for f, wq, _ in series if f]
         for fused, wq, dloop in series * args.repeat:
