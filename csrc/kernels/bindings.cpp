@@ -250,6 +250,14 @@ PYBIND11_MODULE(_kernels, m) {
                                nsplit, sqb, sqh, spb, sps, sph, sgb, sgs, sgh, sab, sob, scale,
                                nw, S(st));
   });
+  m.def("window_decode_attn", [](int dt, ptr q, ptr kc, ptr vc, ptr lens, ptr out, ptr ws, int B,
+                                 int W, int H, int D, int maxlen, int nsplit, long sqb, long sqh,
+                                 long skb, long sks, long skh, long sob, float scale, int nw,
+                                 ptr st) {
+    return fx_window_decode_attn(dt, CP(q), CP(kc), CP(vc), reinterpret_cast<const int*>(lens),
+                                 P(out), F(ws), B, W, H, D, maxlen, nsplit, sqb, sqh, skb, sks,
+                                 skh, sob, scale, nw, S(st));
+  });
   m.def("softmax_fwd", [](int dt, int mdt, ptr x, ptr mask, ptr y, long rows, int Sq, int Sk,
                           long mask_div, float scale, int causal, ptr st) {
     return fx_softmax_fwd(dt, mdt, CP(x), CP(mask), P(y), rows, Sq, Sk, mask_div, scale, causal,
@@ -283,32 +291,32 @@ PYBIND11_MODULE(_kernels, m) {
   // decode-time skinny GEMM with fused sub-layer epilogues (decode_gemv.hip)
   m.def("decode_gemv", [](int dt, int epi, int M, int N, int K, ptr x, long ldx, ptr w, long ldw,
                           ptr bias, ptr res, long ldres, ptr y, long ldy, ptr kc, ptr vc, ptr pos,
-                          int heads, int head_dim, int maxlen, ptr ln_w, ptr ln_b, float ln_eps,
-                          ptr st) {
+                          ptr rows, int heads, int head_dim, int maxlen, ptr ln_w, ptr ln_b,
+                          float ln_eps, ptr st) {
     return fx_decode_gemv(dt, epi, M, N, K, CP(x), ldx, CP(w), ldw, CP(bias), CP(res), ldres, P(y),
-                          ldy, P(kc), P(vc), reinterpret_cast<const long*>(pos), heads, head_dim,
-                          maxlen, CP(ln_w), CP(ln_b), ln_eps, S(st));
+                          ldy, P(kc), P(vc), reinterpret_cast<const long*>(pos),
+                          reinterpret_cast<const int*>(rows), heads, head_dim, maxlen, CP(ln_w), CP(ln_b), ln_eps, S(st));
   });
   // the same with int8 weights and one fp32 scale per output row (decode_gemv_w8.hip)
   m.def("decode_gemv_w8", [](int dt, int epi, int M, int N, int K, ptr x, long ldx, ptr wq, long ldw,
                              ptr wscale, ptr bias, ptr res, long ldres, ptr y, long ldy, ptr kc,
-                             ptr vc, ptr pos, int heads, int head_dim, int maxlen, ptr ln_w,
-                             ptr ln_b, float ln_eps, ptr st) {
+                             ptr vc, ptr pos, ptr rows, int heads, int head_dim, int maxlen,
+                             ptr ln_w, ptr ln_b, float ln_eps, ptr st) {
     return fx_decode_gemv_w8(dt, epi, M, N, K, CP(x), ldx, reinterpret_cast<const int8_t*>(wq), ldw,
                              reinterpret_cast<const float*>(wscale), CP(bias), CP(res), ldres,
-                             P(y), ldy, P(kc), P(vc), reinterpret_cast<const long*>(pos), heads,
-                             head_dim, maxlen, CP(ln_w), CP(ln_b), ln_eps, S(st));
+                             P(y), ldy, P(kc), P(vc), reinterpret_cast<const long*>(pos),
+                             reinterpret_cast<const int*>(rows), heads, head_dim, maxlen, CP(ln_w), CP(ln_b), ln_eps, S(st));
   });
   // the same with packed int4 weights (ldw in bytes) and one fp32 scale per k-group of 256
   // and output row, [K / 256, N] (decode_gemv_w4.hip)
   m.def("decode_gemv_w4", [](int dt, int epi, int M, int N, int K, ptr x, long ldx, ptr wq, long ldw,
                              ptr wscale, ptr bias, ptr res, long ldres, ptr y, long ldy, ptr kc,
-                             ptr vc, ptr pos, int heads, int head_dim, int maxlen, ptr ln_w,
-                             ptr ln_b, float ln_eps, ptr st) {
+                             ptr vc, ptr pos, ptr rows, int heads, int head_dim, int maxlen,
+                             ptr ln_w, ptr ln_b, float ln_eps, ptr st) {
     return fx_decode_gemv_w4(dt, epi, M, N, K, CP(x), ldx, reinterpret_cast<const uint8_t*>(wq), ldw,
                              reinterpret_cast<const float*>(wscale), CP(bias), CP(res), ldres,
-                             P(y), ldy, P(kc), P(vc), reinterpret_cast<const long*>(pos), heads,
-                             head_dim, maxlen, CP(ln_w), CP(ln_b), ln_eps, S(st));
+                             P(y), ldy, P(kc), P(vc), reinterpret_cast<const long*>(pos),
+                             reinterpret_cast<const int*>(rows), heads, head_dim, maxlen, CP(ln_w), CP(ln_b), ln_eps, S(st));
   });
   // CU-masked stream (streams.hip): returns (stream handle, CUs selected)
   m.def("cumask_stream_create", [](int ncu) {

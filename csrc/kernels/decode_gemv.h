@@ -42,7 +42,9 @@ typedef uint32_t uintx4 __attribute__((ext_vector_type(4)));
 //   GV_GELU      y = gelu_tanh(acc + b)                    (FFN1)
 //   GV_RES       y = acc + b + res                         (FFN2 + residual)
 //   GV_QKV       acc + b scattered to q[M, H, D] and the KV cache at this
-//                token's position (k/v_cache[M, maxlen, H, D])   (QKV + cache append)
+//                token's position (k/v_cache[M, maxlen, H, D])   (QKV + cache append);
+//                with a row map, row m goes to cache row rows[m] (several
+//                consecutive tokens of one sample in one call)
 enum { GV_BIAS = 0, GV_GELU = 1, GV_RES = 2, GV_QKV = 3 };
 
 template <typename W>
@@ -58,6 +60,7 @@ struct GemvArgs {
   uint16_t* kc;
   uint16_t* vc;
   const long* pos;
+  const int* rows;  // cache row of x row m; nullptr: row m
   int heads, head_dim, maxlen;
   // optional LayerNorm of x fused as a prologue (LN1 -> QKV, LN2 -> FFN1)
   const uint16_t* ln_w;
@@ -398,7 +401,8 @@ __global__ __launch_bounds__(64 * GV_KS) void gemv_kernel(GemvArgs<W> a) {
       a.y[(long)m * a.ldy + h * D + d] = o;
     } else {
       uint16_t* cache = tq == 1 ? a.kc : a.vc;
-      cache[(((long)m * a.maxlen + a.pos[m]) * a.heads + h) * D + d] = o;
+      const long cr = a.rows != nullptr ? a.rows[m] : m;
+      cache[((cr * a.maxlen + a.pos[m]) * a.heads + h) * D + d] = o;
     }
   } else {
     a.y[(long)m * a.ldy + n] = o;
@@ -466,8 +470,8 @@ inline int env_int(const char* name) {
 template <typename W>
 int gemv_entry(int dt, int epi, int M, int N, int K, const void* x, long ldx,
                const typename W::Ptrs& wp, long ldw, const void* bias, const void* res,
-               long ldres, void* y, long ldy, void* kc, void* vc, const long* pos, int heads,
-               int head_dim, int maxlen, const void* ln_w, const void* ln_b, float ln_eps,
+               long ldres, void* y, long ldy, void* kc, void* vc, const long* pos, const int* rows,
+               int heads, int head_dim, int maxlen, const void* ln_w, const void* ln_b, float ln_eps,
                hipStream_t s) {
   if (M < 1 || M > 16 || N < 1 || K < 1024 || K % 1024 != 0 || (ldx % 8) ||
       (ldw * sizeof(typename W::elt) % 16) || ((uintptr_t)x % 16) || !wp.valid())
@@ -508,7 +512,7 @@ int gemv_entry(int dt, int epi, int M, int N, int K, const void* x, long ldx,
   a.res = (const uint16_t*)res; a.y = (uint16_t*)y;
   a.ldx = ldx; a.ldw = ldw; a.ldy = ldy; a.ldres = ldres;
   a.M = M; a.N = N; a.K = K;
-  a.kc = (uint16_t*)kc; a.vc = (uint16_t*)vc; a.pos = pos;
+  a.kc = (uint16_t*)kc; a.vc = (uint16_t*)vc; a.pos = pos; a.rows = rows;
   a.heads = heads; a.head_dim = head_dim; a.maxlen = maxlen;
   a.ln_w = (const uint16_t*)ln_w; a.ln_b = (const uint16_t*)ln_b; a.ln_eps = ln_eps;
   if (dt == 0) launch_epi<W, bf16>(a, epi, ln, u, ks, rw, s);

@@ -52,10 +52,10 @@ struct W16 {
 
 extern "C" int fx_decode_gemv(int dt, int epi, int M, int N, int K, const void* x, long ldx,
                               const void* w, long ldw, const void* bias, const void* res,
-                              long ldres, void* y, long ldy, void* kc, void* vc, const long* pos,
+                              long ldres, void* y, long ldy, void* kc, void* vc, const long* pos, const int* rows,
                               int heads, int head_dim, int maxlen, const void* ln_w,
                               const void* ln_b, float ln_eps, hipStream_t s) {
   return gemv_entry<W16>(dt, epi, M, N, K, x, ldx, W16::Ptrs{(const uint16_t*)w}, ldw, bias, res,
-                         ldres, y, ldy, kc, vc, pos, heads, head_dim, maxlen, ln_w, ln_b, ln_eps,
+                         ldres, y, ldy, kc, vc, pos, rows, heads, head_dim, maxlen, ln_w, ln_b, ln_eps,
                          s);
 }

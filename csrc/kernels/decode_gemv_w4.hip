@@ -89,9 +89,9 @@ struct W4 {
 extern "C" int fx_decode_gemv_w4(int dt, int epi, int M, int N, int K, const void* x, long ldx,
                                  const uint8_t* wq, long ldw, const float* wscale,
                                  const void* bias, const void* res, long ldres, void* y, long ldy,
-                                 void* kc, void* vc, const long* pos, int heads, int head_dim,
+                                 void* kc, void* vc, const long* pos, const int* rows, int heads, int head_dim,
                                  int maxlen, const void* ln_w, const void* ln_b, float ln_eps,
                                  hipStream_t s) {
   return gemv_entry<W4>(dt, epi, M, N, K, x, ldx, W4::Ptrs{wq, wscale}, ldw, bias, res, ldres, y,
-                        ldy, kc, vc, pos, heads, head_dim, maxlen, ln_w, ln_b, ln_eps, s);
+                        ldy, kc, vc, pos, rows, heads, head_dim, maxlen, ln_w, ln_b, ln_eps, s);
 }

@@ -91,6 +91,9 @@ int fx_beam_decode_attn(int, const void*, const void*, const void*, const int*, 
                         const void*, const int*, const int*, void*, float*, int, int, int, int, int,
                         int, int, long, long, long, long, long, long, long, long, long, long, float,
                         int, hipStream_t);
+int fx_window_decode_attn(int, const void*, const void*, const void*, const int*, void*, float*,
+                          int, int, int, int, int, int, long, long, long, long, long, long, float,
+                          int, hipStream_t);
 void fx_embedding_bwd_sorted(int, const int64_t*, const int64_t*, const void*, float*, int, int,
                              long, long, hipStream_t);
 int fx_softmax_fwd(int, int, const void*, const void*, void*, long, int, int, long, float, int,
@@ -107,13 +110,13 @@ void fx_gemm_set_tune(int);
 void fx_gemm_set_persist(int);
 void fx_gemm_set_xrect(int);
 int fx_decode_gemv(int, int, int, int, int, const void*, long, const void*, long, const void*,
-                   const void*, long, void*, long, void*, void*, const long*, int, int, int,
+                   const void*, long, void*, long, void*, void*, const long*, const int*, int, int, int,
                    const void*, const void*, float, hipStream_t);
 int fx_decode_gemv_w8(int, int, int, int, int, const void*, long, const int8_t*, long, const float*,
-                      const void*, const void*, long, void*, long, void*, void*, const long*, int,
+                      const void*, const void*, long, void*, long, void*, void*, const long*, const int*, int,
                       int, int, const void*, const void*, float, hipStream_t);
 int fx_decode_gemv_w4(int, int, int, int, int, const void*, long, const uint8_t*, long, const float*,
-                      const void*, const void*, long, void*, long, void*, void*, const long*, int,
+                      const void*, const void*, long, void*, long, void*, void*, const long*, const int*, int,
                       int, int, const void*, const void*, float, hipStream_t);
 hipStream_t fx_cumask_stream_create(int, int*);
 int fx_stream_destroy(hipStream_t);

@@ -461,6 +461,192 @@ __global__ __launch_bounds__(64 * NW) void beam_decode_attn_kernel(
   }
 }
 
+// Window decode attention: W consecutive causal queries per sample over one
+// KV cache (the verify step of speculative decoding).
+// q / out: [B*W, H, D] (row strides sqb / sob); caches [B, maxlen, H, D] (skb,
+// sks, skh); lens [B]: keys before the window.  The window's own K/V rows are
+// in the cache at lens[b] .. lens[b]+W-1; row b*W + j attends to keys
+// [0, lens[b] + j].  lens[b] + W <= maxlen is trusted.  Every row below
+// lens[b] + W is loaded and enters masked queries as 0 * v, so those rows must
+// hold finite values; rows at or beyond lens[b] + W are never read.
+// One workgroup owns all W queries of one (b, h, split), as the beam kernel
+// owns its beams: a K/V row is loaded once (16-byte loads, U rows in flight per
+// lane group, the next step's rows requested before this step is scored) and
+// scored against every query.  The causal limit is a per-(query, key) select.
+// NQ >= W queries are held in registers (5 and 7 run the 6 and 8 query code
+// with query 0 repeated and not stored).  U per NQ is the beam kernel's choice,
+// carried over and not measured again for this kernel.
+// Slot invariance: a query's result depends only on its q row and the keys it
+// sees, not on its slot j.  The split bounds are multiples of chunk (a function
+// of maxlen and nsplit), the key -> (step, wave, lane group, u) map is a
+// function of the absolute key index, and a step in which a query sees no key
+// leaves its state as it is: the score is NEG (finite), so mx = m, exp(m - mx)
+// = 1 and every product added is 0.
+// Partials go to ws as [(row*H + h)*nsplit + split][D+2]: decode_attn_combine_kernel
+// merges them with its "batch" = B*W.
+template <typename T, int D, int NQ, int NW>
+__global__ __launch_bounds__(64 * NW) void window_decode_attn_kernel(
+    const uint16_t* __restrict__ q, const uint16_t* __restrict__ kc,
+    const uint16_t* __restrict__ vc, const int* __restrict__ lens, float* __restrict__ ws,
+    uint16_t* __restrict__ out, int H, int W, int nsplit, int chunk, long sqb, long sqh, long skb,
+    long sks, long skh, long sob, float scale) {
+  constexpr int LPK = D / 8;                     // lanes per key row
+  constexpr int KPW = 64 / LPK;                  // key rows per wave instruction
+  constexpr int U = NQ <= 2 ? 4 : NQ <= 4 ? 2 : 1;  // rows per lane group per step
+  constexpr int RB = NQ * NW <= 32 ? NQ : (32 / NW > 0 ? 32 / NW : 1);  // queries per merge round
+  const int split = blockIdx.x % nsplit, bh = blockIdx.x / nsplit;
+  const int b = bh / H, hd = bh % H;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int sub = lane / LPK, c = (lane % LPK) * 8;
+  const int len0 = lens[b];
+  const int k_lo = split * chunk, k_hi = min(len0 + W, k_lo + chunk);
+  constexpr float NEG = -1e30f;  // "no key yet": finite, so exp(m - mx) never sees inf - inf
+  const long row0 = (long)b * W;
+  float qv[NQ][8], o[NQ][8], m[NQ], l[NQ];
+#pragma unroll
+  for (int j = 0; j < NQ; ++j) {
+    load8<T>(q + (row0 + (j < W ? j : 0)) * sqb + hd * sqh + c, qv[j]);
+    m[j] = NEG;
+    l[j] = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      qv[j][i] *= scale;
+      o[j][i] = 0.f;
+    }
+  }
+  const uint16_t* kb = kc + b * skb + hd * skh + c;
+  const uint16_t* vb = vc + b * skb + hd * skh + c;
+  constexpr int STEP = NW * KPW * U;
+  uint4 kraw[U], vraw[U], knext[U], vnext[U];
+  if (k_lo < k_hi) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int key = k_lo + (u * NW + w) * KPW + sub;
+      const int kk = key < k_hi ? key : k_lo;  // in-range dummy row
+      kraw[u] = *reinterpret_cast<const uint4*>(kb + (long)kk * sks);
+      vraw[u] = *reinterpret_cast<const uint4*>(vb + (long)kk * sks);
+    }
+  }
+  for (int k0 = k_lo; k0 < k_hi; k0 += STEP) {
+    const bool more = k0 + STEP < k_hi;
+    if (more) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int key = k0 + STEP + (u * NW + w) * KPW + sub;
+        const int kk = key < k_hi ? key : k_lo;
+        knext[u] = *reinterpret_cast<const uint4*>(kb + (long)kk * sks);
+        vnext[u] = *reinterpret_cast<const uint4*>(vb + (long)kk * sks);
+      }
+    }
+    // key u is visible to query j iff it lies in this split and key <= len0 + j,
+    // i.e. j >= jmin[u] (NQ for a key outside the split)
+    int jmin[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int key = k0 + (u * NW + w) * KPW + sub;
+      jmin[u] = key < k_hi ? key - len0 : NQ;
+    }
+    float kv[U][8], vv[U][8];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      unpack8<T>(kraw[u], kv[u]);
+      unpack8<T>(vraw[u], vv[u]);
+    }
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) {
+      float sc[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        sc[u] = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) sc[u] += kv[u][i] * qv[j][i];
+      }
+      float mx = m[j];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const float t = group_sum<LPK>(sc[u]);
+        sc[u] = j >= jmin[u] ? t : NEG;
+        mx = fmaxf(mx, sc[u]);
+      }
+      const float a = __expf(m[j] - mx);
+      l[j] *= a;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) o[j][i] *= a;
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const float p = j >= jmin[u] ? __expf(sc[u] - mx) : 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) o[j][i] += p * vv[u][i];
+        l[j] += p;
+      }
+      m[j] = mx;
+    }
+    if (more) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        kraw[u] = knext[u];
+        vraw[u] = vnext[u];
+      }
+    }
+  }
+  // a state that saw no key is (-inf, 0, 0), as merge_state and the combine pass expect
+#pragma unroll
+  for (int j = 0; j < NQ; ++j) m[j] = l[j] > 0.f ? m[j] : -INFINITY;
+  // ---- merge: lane groups of a wave by shuffles, then the waves through LDS
+#pragma unroll
+  for (int j = 0; j < NQ; ++j) {
+#pragma unroll
+    for (int off = LPK; off < 64; off <<= 1) {
+      float o2[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) o2[i] = __shfl_xor(o[j][i], off, 64);
+      const float m2 = __shfl_xor(m[j], off, 64), l2 = __shfl_xor(l[j], off, 64);
+      merge_state(m[j], l[j], o[j], m2, l2, o2);
+    }
+  }
+  __shared__ float sm_m[RB][NW * LPK], sm_l[RB][NW * LPK], sm_o[RB][NW * LPK][8];
+#pragma unroll
+  for (int r0 = 0; r0 < NQ; r0 += RB) {
+    if (r0 > 0) __syncthreads();
+    if (lane < LPK) {
+#pragma unroll
+      for (int r = 0; r < RB; ++r) {
+        if (r0 + r >= NQ) continue;
+        sm_m[r][w * LPK + lane] = m[r0 + r];
+        sm_l[r][w * LPK + lane] = l[r0 + r];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) sm_o[r][w * LPK + lane][i] = o[r0 + r][i];
+      }
+    }
+    __syncthreads();
+    // thread t merges query r0 + t / LPK, column slice t % LPK
+    const int r = threadIdx.x / LPK, sl = threadIdx.x % LPK, j = r0 + r;
+    if (r < RB && j < W) {
+      float M = -INFINITY, L = 0.f, O[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) O[i] = 0.f;
+#pragma unroll
+      for (int i = 0; i < NW; ++i)
+        merge_state(M, L, O, sm_m[r][i * LPK + sl], sm_l[r][i * LPK + sl], sm_o[r][i * LPK + sl]);
+      if (nsplit == 1) {  // one split: normalise and store the output directly
+        const float inv = L > 0.f ? 1.f / L : 0.f;
+        float res[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) res[i] = O[i] * inv;
+        store8<T>(out + (row0 + j) * sob + hd * D + sl * 8, res);
+      } else {
+        float* wp = ws + (((row0 + j) * H + hd) * nsplit + split) * (D + 2);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) wp[sl * 8 + i] = O[i];
+        if (sl == 0) {
+          wp[D] = M;
+          wp[D + 1] = L;
+        }
+      }
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" void fx_absmax(int dtype, const void* x, long n, float* out, hipStream_t st) {
@@ -576,5 +762,58 @@ extern "C" int fx_beam_decode_attn(int dt, const void* q, const void* kp, const 
   }
 #undef FX_BEAM_NB
 #undef FX_BEAM
+  return 0;
+}
+
+// Window decode attention (see window_decode_attn_kernel).  dt: 0 bf16 / 1 fp16;
+// W: queries per sample, 1..8; chunk = keys per split of the maxlen key axis; ws:
+// fp32 workspace of B*W*H*nsplit*(D+2); nw: waves per workgroup, 4 or 8, 0 = by
+// the number of workgroups.
+extern "C" int fx_window_decode_attn(int dt, const void* q, const void* kc, const void* vc,
+                                     const int* lens, void* out, float* ws, int B, int W, int H,
+                                     int D, int maxlen, int nsplit, long sqb, long sqh, long skb,
+                                     long sks, long skh, long sob, float scale, int nw,
+                                     hipStream_t st) {
+  if (D != 64 && D != 128) return -1;
+  if (nsplit < 1) return -2;
+  if (dt != 0 && dt != 1) return -3;
+  if (W < 1 || W > 8) return -4;
+  if (nw != 0 && nw != 4 && nw != 8) return -5;
+  const int chunk = (maxlen + nsplit - 1) / nsplit;
+  const int g = B * H * nsplit;
+  const bool wide = nw == 8 || (nw == 0 && g <= 256);
+#define FX_WIN(TT, DD, NQQ)                                                                      \
+  do {                                                                                           \
+    if (wide)                                                                                    \
+      window_decode_attn_kernel<TT, DD, NQQ, 8><<<g, 512, 0, st>>>(                              \
+          (const uint16_t*)q, (const uint16_t*)kc, (const uint16_t*)vc, lens, ws,                \
+          (uint16_t*)out, H, W, nsplit, chunk, sqb, sqh, skb, sks, skh, sob, scale);             \
+    else                                                                                         \
+      window_decode_attn_kernel<TT, DD, NQQ, 4><<<g, 256, 0, st>>>(                              \
+          (const uint16_t*)q, (const uint16_t*)kc, (const uint16_t*)vc, lens, ws,                \
+          (uint16_t*)out, H, W, nsplit, chunk, sqb, sqh, skb, sks, skh, sob, scale);             \
+  } while (0)
+#define FX_WIN_NQ(TT, DD)                                                                        \
+  do {                                                                                           \
+    switch (W) {                                                                                 \
+      case 1: FX_WIN(TT, DD, 1); break;                                                          \
+      case 2: FX_WIN(TT, DD, 2); break;                                                          \
+      case 3: FX_WIN(TT, DD, 3); break;                                                          \
+      case 4: FX_WIN(TT, DD, 4); break;                                                          \
+      case 5:                                                                                    \
+      case 6: FX_WIN(TT, DD, 6); break;                                                          \
+      default: FX_WIN(TT, DD, 8); break;                                                         \
+    }                                                                                            \
+    if (nsplit > 1)                                                                              \
+      decode_attn_combine_kernel<TT, DD><<<B * W * H, DD, 0, st>>>(ws, (uint16_t*)out, H,        \
+                                                                   nsplit, sob);                 \
+  } while (0)
+  if (dt == 0) {
+    if (D == 128) FX_WIN_NQ(bf16, 128); else FX_WIN_NQ(bf16, 64);
+  } else {
+    if (D == 128) FX_WIN_NQ(f16, 128); else FX_WIN_NQ(f16, 64);
+  }
+#undef FX_WIN_NQ
+#undef FX_WIN
   return 0;
 }

@@ -19,7 +19,12 @@ MI355X design (K18/K19):
   (``ops.decode_attention``) that streams the cache once;
 * beam search (which the reference accepts and then raises on) keeps the
   prompt's K/V once per sample and the beams as an ancestor table
-  (``BeamKVCache``, ``ops.beam_decode_attention``): a reorder moves no K/V.
+  (``BeamKVCache``, ``ops.beam_decode_attention``): a reorder moves no K/V;
+* speculative greedy decoding (``spec_draft`` / ``set_drafter``) drafts on
+  quantised copies of the model's own weights and verifies ``spec_tokens + 1``
+  positions per sample in one window step of the target weights (a cache-row
+  map in the QKV GEMV epilogue, ``ops.window_decode_attention``): the target's
+  ids and scores, whatever the drafter proposes.
 """
 import os
 import warnings
@@ -231,20 +236,25 @@ def _layer_prefill(layer, x, cache, li, lens):
     return ops.bias_dropout_add(m, mb, x2)
 
 
-def _layer_decode(layer, x, cache, li, pos, lens_after):
+def _layer_decode(layer, x, cache, li, pos, lens_after, rows=None):
     """One-token pass: x [B, 1, h]; writes K/V at ``pos`` [B] and attends.  With
     a ``BeamKVCache`` ``pos`` is the generated slot per row and ``lens_after``
-    the valid slots per sample."""
+    the valid slots per sample.  Window form (``rows`` int32 [B*W], the cache
+    row of every x row): x [B*W, 1, h], K/V go to ``cache[rows, pos]`` and
+    ``lens_after`` [B] counts the keys before the window."""
     attn = layer.attn
     h = layer.ln1(x)
     qkv = attn.qkv_proj(h)
     b = qkv.shape[0]
     qkv5 = qkv.view(b, attn.heads, 3, attn.head_dim)
-    ar = torch.arange(b, device=x.device)
+    ar = torch.arange(b, device=x.device) if rows is None else rows.long()
     kc, vc = _gen_kv(cache, li)
     kc[ar, pos] = qkv5[:, :, 1]
     vc[ar, pos] = qkv5[:, :, 2]
-    o = _attend(cache, li, qkv5[:, :, 0].contiguous(), lens_after)
+    if rows is None:
+        o = _attend(cache, li, qkv5[:, :, 0].contiguous(), lens_after)
+    else:
+        o = ops.window_decode_attention(qkv5[:, :, 0].contiguous(), kc, vc, lens_after)
     a, ab = attn.out_proj(o.reshape(b, 1, -1))
     x2, h2 = ops.add_layer_norm(a, ab, x, layer.ln2.weight, layer.ln2.bias, layer.ln2.eps)
     m, mb = layer.mlp(h2)
@@ -285,7 +295,7 @@ def _dlin(G, x, lin, epi, q8, **kw):
     return G.decode_linear(x, lin.weight, lin.bias, epi, **kw)
 
 
-def _layer_decode_fused(layer, x, cache, li, pos, lens_after, w8=None):
+def _layer_decode_fused(layer, x, cache, li, pos, lens_after, w8=None, rows=None):
     """One-token pass as four GEMV launches and the attention (K19, the
     fused_multi_transformer counterpart): [LN1 + QKV GEMV + bias, K/V appended
     to the cache in the epilogue] -> split-K decode attention -> [out-proj
@@ -294,20 +304,27 @@ def _layer_decode_fused(layer, x, cache, li, pos, lens_after, w8=None):
     normalises the few rows into LDS); shapes the fused prologue does not
     cover fall back to a separate LayerNorm launch.  Returns None when a GEMV
     does not cover the shape (batch > 16).  ``w8`` (``weight_quant``) maps
-    ``qkv_proj`` / ``out_proj`` / ``fc1`` / ``fc2`` to this layer's quantised copies."""
+    ``qkv_proj`` / ``out_proj`` / ``fc1`` / ``fc2`` to this layer's quantised copies.
+    Window form (``rows`` int32 [B*W]): the QKV epilogue appends row ``m`` to
+    ``cache[rows[m], pos[m]]`` and the attention is the window kernel with
+    ``lens_after`` [B] keys before the window."""
     from ....ops import gemm as G
     attn, mlp = layer.attn, layer.mlp
     w8 = w8 or {}
     B, h = x.shape[0], x.shape[-1]
     x2d = x.reshape(B, h)
-    kv = _gen_kv(cache, li) + (pos,)
+    kv = _gen_kv(cache, li) + ((pos,) if rows is None else (pos, rows))
     q = _dlin(G, x2d, attn.qkv_proj, G.GV_QKV, w8.get("qkv_proj"), qkv_cache=kv,
               ln=(layer.ln1.weight, layer.ln1.bias, layer.ln1.eps)) if _LN_FUSE else None
     if q is None:
         q = _dlin(G, layer.ln1(x2d), attn.qkv_proj, G.GV_QKV, w8.get("qkv_proj"), qkv_cache=kv)
     if q is None:
         return None
-    o = _attend(cache, li, q.view(B, attn.heads, attn.head_dim), lens_after)
+    if rows is None:
+        o = _attend(cache, li, q.view(B, attn.heads, attn.head_dim), lens_after)
+    else:
+        o = ops.window_decode_attention(q.view(B, attn.heads, attn.head_dim), kv[0], kv[1],
+                                        lens_after)
     x2 = _dlin(G, o.view(B, -1), attn.out_proj, G.GV_RES, w8.get("out_proj"), res=x2d)
     f = _dlin(G, x2, mlp.fc1, G.GV_GELU, w8.get("fc1"),
               ln=(layer.ln2.weight, layer.ln2.bias, layer.ln2.eps)) if _LN_FUSE else None
@@ -397,6 +414,70 @@ class _GraphedSelectStep(_GraphedDecodeStep):
         return logits
 
 
+class _GraphedWindowStep(_GraphedDecodeStep):
+    """The window decode step (``_window_step``) under the same capture-once /
+    replay scheme: tokens, cache positions and ``lens`` are static tensors; the
+    row map is constant (row ``b*W + j`` belongs to sample ``b``)."""
+
+    def __init__(self, gen, cache, batch, window):
+        super().__init__(gen, cache, batch * window)
+        dev = self.nxt.device
+        self.rows = torch.arange(batch, dtype=torch.int32, device=dev).repeat_interleave(window)
+        self.lens = torch.zeros(batch, dtype=torch.int32, device=dev)
+
+    def __call__(self, tok, pos, lens):
+        self.lens.copy_(lens)
+        return super().__call__(tok, pos)
+
+    def _run(self):
+        return self.gen._window_step(self.nxt, self.cur, self.rows, self.lens, self.cache)
+
+
+class _GraphedDraftStep(_GraphedDecodeStep):
+    """One draft token as one graph: a plain decode step on the draft copies
+    (LM head included), the argmax, and the advance of the step's own inputs
+    ``nxt`` / ``cur``, so ``k`` replays draft ``k`` tokens with no host work
+    between them."""
+
+    def _run(self):
+        gen, cur = self.gen, self.cur
+        ids = cur.clamp(max=gen.gpt.cfg.max_position_embeddings - 1)
+        logits = gen._step(self.nxt, ids, self.cache, cur, (cur + 1).to(torch.int32),
+                           copies=gen._wd)
+        self.nxt.copy_(torch.argmax(logits, -1))
+        cur.add_(1)
+        return logits
+
+
+class _QuantDrafter:
+    """The built-in drafter of speculative decoding: ``k`` greedy decode steps
+    on the ``spec_draft`` copies of the model's own weights.  It writes its
+    K/V into the shared cache at ``cur .. cur+k-1``; the verify step
+    overwrites those rows with the target's."""
+
+    def __init__(self, gen):
+        self.gen = gen
+        self.step = None
+
+    def propose(self, last, cur, cache, k):
+        if self.step is None or self.step.cache is not cache:
+            self.step = _GraphedDraftStep(self.gen, cache, last.shape[0])
+        st = self.step
+        st.nxt.copy_(last)
+        st.cur.copy_(cur)
+        out = torch.empty(last.shape[0], k, dtype=torch.long, device=last.device)
+        for i in range(k):
+            if self.gen.use_hip_graph:
+                st._capture_or_replay()
+            else:
+                st._run()
+            out[:, i] = st.nxt
+        return out
+
+    def release(self):
+        self.step = None
+
+
 class GPTForGeneration(torch.nn.Module):
     def __init__(self, pretrain_model, configs):
         super().__init__()
@@ -438,6 +519,23 @@ class GPTForGeneration(torch.nn.Module):
         self._device_loop_warned = False
         if self.decode_strategy not in ("sampling", "greedy_search", "beam_search"):
             raise ValueError("decode_strategy must be sampling, greedy_search or beam_search")
+        # speculative greedy decoding: draft on quantised copies, verify spec_tokens + 1
+        # positions in one window step of the target weights
+        self.spec_draft = c.get("spec_draft")
+        self.spec_tokens = int(c.get("spec_tokens", 4))
+        self._wd = None        # the draft's copies, laid out like _w8
+        self._drafter = None   # installed by set_drafter
+        self._quant_drafter = None
+        self._spec_warned = False
+        self.last_spec_stats = None
+        if self.spec_draft is not None:
+            if self.spec_draft not in _WEIGHT_QUANT:
+                raise ValueError("spec_draft must be None, %s (got %r)"
+                                 % (" or ".join(repr(k) for k in _WEIGHT_QUANT), self.spec_draft))
+            if self.spec_draft == self.weight_quant:
+                raise ValueError("spec_draft must differ from weight_quant (%r): a draft in the "
+                                 "target's format saves nothing" % (self.weight_quant,))
+            self._spec_check()
         if self.decode_strategy == "beam_search":
             if self.num_beam_groups > 1:
                 raise ValueError("diverse beam search (num_beam_groups > 1) is not supported yet")
@@ -446,6 +544,25 @@ class GPTForGeneration(torch.nn.Module):
             if self.num_return_sequences > self.num_beams:
                 raise ValueError("num_return_sequences (%d) must not exceed num_beams (%d)"
                                  % (self.num_return_sequences, self.num_beams))
+
+    def _spec_check(self):
+        if not 1 <= self.spec_tokens <= 7:
+            raise ValueError("spec_tokens must be in 1..7 (got %r)" % (self.spec_tokens,))
+        if self.decode_strategy != "greedy_search" or self.device_loop \
+                or self.num_return_sequences > 1:
+            raise ValueError("speculative decoding supports greedy_search only, without "
+                             "device_loop and with num_return_sequences 1")
+
+    def set_drafter(self, drafter):
+        """Install the drafter of speculative greedy decoding (any device): an
+        object with ``propose(last, cur, cache, k) -> LongTensor [B, k]``, the
+        ``k`` tokens it expects after ``last`` [B], which sits at position
+        ``cur`` [B] and is not in ``cache`` yet.  It may write cache rows
+        ``cur .. cur+k-1``; the verify step overwrites them.  The output is
+        the target's whatever it proposes.  ``None`` removes it."""
+        if drafter is not None:
+            self._spec_check()
+        self._drafter = drafter
 
     def _processors(self, max_len):
         procs = LogitsProcessorList()
@@ -475,46 +592,50 @@ class GPTForGeneration(torch.nn.Module):
         return per_layer, self.gpt.embeddings.word_embeddings.weight
 
     def requantize(self):
-        """(Re)build the quantised copies from the current 16-bit weights.  The
+        """(Re)build the quantised copies from the current 16-bit weights: the
+        target's (``weight_quant``) and the draft's (``spec_draft``).  The
         16-bit weights stay resident (prefill and the embedding lookup use
         them): the quantised path buys decode bandwidth, not memory.  Returns
         True when the quantised path is active; on CPU or under tensor parallel
-        the key is accepted and ignored with one warning (those paths do not
+        the keys are accepted and ignored with one warning (those paths do not
         stream weights through the decode GEMV).  A weight the format cannot
         hold (int4: K no multiple of the group size) keeps no copy and decodes
         on its 16-bit weight."""
-        if self.weight_quant is None:
+        if self.weight_quant is None and self.spec_draft is None:
             return False
         head = self.gpt.embeddings.word_embeddings.weight
         if not head.is_cuda or topo.mp_world_size() != 1 or not self.fused_decode:
-            if not self._w8_warned:
+            if self.weight_quant is not None and not self._w8_warned:
                 warnings.warn("weight_quant=%r is ignored: the quantised decode path needs a GPU, "
                               "fused_decode and no tensor parallelism" % (self.weight_quant,))
                 self._w8_warned = True
-            self._w8, self._w8_src = None, []
+            self._w8, self._wd, self._w8_src = None, None, []
             return False
         per_layer, head = self._w8_sources()
-        src = []
+        self._w8_src = [(w, w._version, w.data_ptr())
+                        for w in [w for d in per_layer for w in d.values()] + [head]]
 
-        quantiser, gemv, group = _WEIGHT_QUANT[self.weight_quant]
-
-        def quant(w):
-            src.append((w, w._version, w.data_ptr()))
-            if w.shape[1] % group:
+        def copies(fmt):
+            if fmt is None:
                 return None
-            return (gemv,) + getattr(ops, quantiser)(w)
+            quantiser, gemv, group = _WEIGHT_QUANT[fmt]
+
+            def quant(w):
+                if w.shape[1] % group:
+                    return None
+                return (gemv,) + getattr(ops, quantiser)(w)
+            return {"layers": [{k: quant(w) for k, w in d.items()} for d in per_layer],
+                    "head": quant(head)}
         with torch.no_grad():
-            self._w8 = {"layers": [{k: quant(w) for k, w in d.items()} for d in per_layer],
-                        "head": quant(head)}
-        self._w8_src = src
+            self._w8, self._wd = copies(self.weight_quant), copies(self.spec_draft)
         return True
 
     def _w8_refresh(self):
         """At the start of ``generate()``: quantise on first use and whenever a
         source weight was written in place or replaced since."""
-        if self.weight_quant is None or self._w8_warned:
+        if (self.weight_quant is None or self._w8_warned) and self.spec_draft is None:
             return
-        stale = self._w8 is None
+        stale = self._w8 is None and self._wd is None
         if not stale:
             cur = [w for d in self._w8_sources()[0] for w in d.values()]
             cur.append(self.gpt.embeddings.word_embeddings.weight)
@@ -537,21 +658,35 @@ class GPTForGeneration(torch.nn.Module):
         slots; return fp32 logits [B*nb, V]."""
         return self._step(nxt, pos, cache, slot, glens)
 
-    def _step(self, nxt, pos, cache, wpos, after):
+    def _window_step(self, tok, pos, rows, lens, cache):
+        """Window decode step: ``W`` consecutive tokens per sample in one pass.
+        ``tok`` [B*W] sits at cache position ``pos`` [B*W] (= ``lens[b] + j``)
+        of cache row ``rows`` int32 [B*W] (= ``b``); ``lens`` int32 [B] keys
+        precede the window.  Appends the B*W K/V rows and returns fp32 logits
+        [B*W, V]; row ``b*W + j`` sees the cache up to its own position.
+        Position ids past ``max_position_embeddings`` are clamped (such slots
+        are never emitted)."""
+        ids = pos.clamp(max=self.gpt.cfg.max_position_embeddings - 1)
+        return self._step(tok, ids, cache, pos, lens, rows=rows)
+
+    def _step(self, nxt, pos, cache, wpos, after, rows=None, copies=None):
+        """``rows``: window form (see ``_window_step``).  ``copies``: the
+        quantised copies to stream (default: the target's, ``weight_quant``)."""
+        q8 = self._w8 if copies is None else copies
         x = ops.embedding(nxt[:, None], self.gpt.embeddings.word_embeddings.weight,
                           pos[:, None], self.gpt.embeddings.position_embeddings, 0) \
             if topo.mp_world_size() == 1 else self.gpt.embeddings(nxt[:, None], pos[:, None])
         fused = self.fused_decode and x.is_cuda and x.shape[0] <= 16
-        w8 = self._w8["layers"] if self._w8 is not None else None
+        w8 = q8["layers"] if q8 is not None else None
         for li, layer in enumerate(self.gpt.layers):
             if fused and _fusable(layer):
-                y = _layer_decode_fused(layer, x, cache, li, wpos, after, w8[li]) if w8 \
-                    else _layer_decode_fused(layer, x, cache, li, wpos, after)
+                y = _layer_decode_fused(layer, x, cache, li, wpos, after, w8[li] if w8 else None,
+                                        rows)
             else:
                 y = None
-            x = y if y is not None else _layer_decode(layer, x, cache, li, wpos, after)
+            x = y if y is not None else _layer_decode(layer, x, cache, li, wpos, after, rows)
         x = self.gpt.final_ln(x)
-        return self._logits(x[:, 0], self._w8["head"] if self._w8 is not None else None)
+        return self._logits(x[:, 0], q8["head"] if q8 is not None else None)
 
     def _logits(self, h, q8=None):
         """``q8``: the quantised copy of the tied table (decode steps; the prefill's
@@ -601,7 +736,10 @@ class GPTForGeneration(torch.nn.Module):
         total = min(int(lens.max().item()) + max_new, cfg.max_position_embeddings)
         p = next(self.parameters())
         attn0 = self.gpt.layers[0].attn
-        cache = KVCache(len(self.gpt.layers), B, total, attn0.heads, attn0.head_dim, p.dtype, dev)
+        drafter = self._spec_drafter(B, dev)
+        # speculative rounds write spec_tokens rows past the last emitted position
+        rows = total + (self.spec_tokens if drafter is not None else 0)
+        cache = KVCache(len(self.gpt.layers), B, rows, attn0.heads, attn0.head_dim, p.dtype, dev)
         gen = None
         if seed is not None:
             gen = torch.Generator(device=dev)
@@ -622,6 +760,8 @@ class GPTForGeneration(torch.nn.Module):
             if not self._device_loop_warned:
                 warnings.warn("device_loop is ignored under tensor parallelism")
                 self._device_loop_warned = True
+        if drafter is not None:
+            return self._speculative(input_ids, lens, logits, cache, max_new, pad, total, drafter)
         procs = self._processors(max_new)
         unfinished = torch.ones(B, dtype=torch.bool, device=dev)
         scores = torch.zeros(B, device=dev)
@@ -673,6 +813,163 @@ class GPTForGeneration(torch.nn.Module):
         if not out_tokens:
             return torch.zeros(B, 0, dtype=torch.long, device=dev), scores
         return torch.stack(out_tokens, 1), scores
+
+    # ---- speculative greedy decoding (spec_draft / set_drafter)
+    def _spec_drafter(self, batch, dev):
+        """The drafter of this ``generate()`` call, or None for the plain loop:
+        no drafter configured, or the window step does not cover the call (then
+        the key is ignored with one warning, as ``weight_quant`` is)."""
+        self.last_spec_stats = None
+        if self._drafter is None and self.spec_draft is None:
+            return None
+        reason = None
+        if topo.mp_world_size() != 1:
+            reason = "tensor parallelism"
+        elif batch * (self.spec_tokens + 1) > 16:
+            reason = "batch * (spec_tokens + 1) = %d rows exceed the 16 of the decode GEMV" \
+                % (batch * (self.spec_tokens + 1))
+        elif self._drafter is None and (dev.type != "cuda" or not self.fused_decode):
+            reason = "the quantised draft needs a GPU and fused_decode"
+        if reason is not None:
+            if not self._spec_warned:
+                warnings.warn("speculative decoding is ignored (%s): the plain loop runs" % reason)
+                self._spec_warned = True
+            return None
+        if self._drafter is not None:
+            return self._drafter
+        if self._quant_drafter is None:
+            self._quant_drafter = _QuantDrafter(self)
+        return self._quant_drafter
+
+    def _spec_process(self, logits, hist, valid, step, max_new):
+        """The logits processors of ``_processors`` for one window slot, with a
+        step index and a history per row: ``hist`` [B, L] with ``valid`` [B, L]
+        marking the row's tokens so far, ``step`` [B] the index of the token
+        these logits choose.  Forced BOS acts on step 0 only, which the prefill
+        logits choose.  Returns a processed copy."""
+        lj = logits.clone()
+        eos = self.eos_token_id
+        if self.min_length and eos is not None:
+            lj[:, eos] = torch.where(step < self.min_length, torch.full_like(lj[:, eos], -1e9),
+                                     lj[:, eos])
+        if self.repetition_penalty and self.repetition_penalty != 1.0:
+            # tokens outside the history point at the row's first token (a duplicate
+            # index that carries the same value)
+            ids = torch.where(valid, hist, hist[:, :1])
+            sc = torch.gather(lj, 1, ids)
+            sc = torch.where(sc < 0, sc * self.repetition_penalty, sc / self.repetition_penalty)
+            lj.scatter_(1, ids, sc)
+        if self.forced_eos_token_id is not None:
+            f = step == max_new - 1
+            lj = torch.where(f[:, None], torch.full_like(lj, -1e9), lj)
+            col = lj[:, self.forced_eos_token_id]
+            lj[:, self.forced_eos_token_id] = torch.where(f, torch.zeros_like(col), col)
+        return lj
+
+    def _speculative(self, input_ids, lens, logits, cache, max_new, pad, total, drafter):
+        """Greedy search in rounds of {draft ``spec_tokens`` tokens, verify them
+        and one more position in one window step of the target weights, keep
+        the longest agreeing prefix plus the target's next token}.  ``logits``
+        are the prefill's (they choose token 0).
+
+        Every emitted token is the argmax of processed target logits, so ids
+        and scores are the target's; the drafter only decides how many window
+        steps are run.  Past the first token every cache row is written by a
+        window step of ``B * (spec_tokens + 1)`` rows, whose row results do not
+        depend on the slot, so the output does not depend on the drafter
+        either.  One host read per round (is any row still emitting).
+
+        ``last_spec_stats``: ``rounds``; ``drafted`` = ``spec_tokens * B`` per
+        round (finished rows keep their rows and are drafted too);
+        ``accepted`` = the leading draft tokens the target agreed with, over
+        the rows still emitting (agreement in slots past ``max_dec_len``
+        counts, those tokens are not emitted)."""
+        dev = input_ids.device
+        B, S = input_ids.shape
+        eos = self.eos_token_id
+        g = self.spec_tokens
+        W = g + 1
+        T = max(0, total - int(lens.max().item()))  # tokens the plain loop emits without EOS
+        stats = {"rounds": 0, "drafted": 0, "accepted": 0}
+        self.last_spec_stats = stats
+        scores = torch.zeros(B, device=dev)
+        if T == 0:
+            return torch.zeros(B, 0, dtype=torch.long, device=dev), scores
+        # ---- token 0, from the prefill logits, as the plain loop takes it
+        procs = self._processors(max_new)
+        for pr in procs:
+            if hasattr(pr, "cur_len"):
+                pr.cur_len = 0
+        logits = procs(input_ids, logits)
+        last = torch.argmax(logits, -1)
+        scores = torch.log_softmax(logits, -1).gather(1, last[:, None]).squeeze(1)
+        # W slack columns: a row's window may reach past the last emitted token
+        out = torch.full((B, T + W), pad, dtype=torch.long, device=dev)
+        out[:, 0] = last
+        hist = torch.cat([input_ids, out], 1)        # the plain loop's history, per row
+        unfinished = torch.ones(B, dtype=torch.bool, device=dev)
+        if eos is not None:
+            unfinished = last != eos
+        emitted = torch.ones(B, dtype=torch.long, device=dev)
+        cur = lens.clone()                           # position of `last` (not in the cache yet)
+        ar = torch.arange(W, device=dev)
+        cols = torch.arange(hist.shape[1], device=dev)[None, :]
+        accepted = torch.zeros((), dtype=torch.long, device=dev)
+        graphed = None
+        if self.use_hip_graph and dev.type == "cuda":
+            graphed = _GraphedWindowStep(self, cache, B, W)
+        rows = torch.arange(B, dtype=torch.int32, device=dev).repeat_interleave(W)
+        plain_logits = all(isinstance(pr, ForcedBOSTokenLogitsProcessor) for pr in procs)
+        while True:
+            active = unfinished & (emitted < T)
+            if not bool(active.any()):
+                break
+            d = drafter.propose(last, cur, cache, g).to(device=dev, dtype=torch.long)
+            tok = torch.cat([last[:, None], d], 1).reshape(-1)
+            pos = (cur[:, None] + ar[None, :]).reshape(-1)
+            before = cur.to(torch.int32)
+            lg = graphed(tok, pos, before) if graphed is not None else \
+                self._window_step(tok, pos, rows, before, cache)
+            lg = lg.view(B, W, -1)
+            # slot j chooses token emitted + j from the history plus d_1 .. d_j
+            idx = emitted[:, None] + ar[None, :]
+            hist.scatter_(1, S + idx[:, :g], d)
+            if plain_logits:  # no processor acts past token 0: all slots at once
+                t = torch.argmax(lg, -1)
+                lp = torch.log_softmax(lg, -1).gather(2, t[:, :, None]).squeeze(2)
+            else:
+                t = torch.empty(B, W, dtype=torch.long, device=dev)
+                lp = torch.empty(B, W, device=dev)
+                for j in range(W):
+                    step = emitted + j
+                    lj = self._spec_process(lg[:, j], hist, cols < (S + step)[:, None], step,
+                                            max_new)
+                    t[:, j] = torch.argmax(lj, -1)
+                    lp[:, j] = torch.log_softmax(lj, -1).gather(1, t[:, j:j + 1]).squeeze(1)
+            n = (d == t[:, :g]).long().cumprod(1).sum(1)      # accepted draft tokens
+            m = torch.minimum(n + 1, T - emitted)
+            emit = (ar[None, :] < m[:, None]) & active[:, None]
+            if eos is not None:  # stop at the first EOS inside the accepted window
+                hit = emit & (t == eos)
+                done = hit.any(1)
+                first = torch.where(hit, ar[None, :], W).min(1).values
+                m = torch.where(done, first + 1, m)
+                emit = (ar[None, :] < m[:, None]) & active[:, None]
+                unfinished = unfinished & ~done
+            out.scatter_(1, idx, torch.where(emit, t, out.gather(1, idx)))
+            hist.scatter_(1, S + idx, torch.where(emit, t, hist.gather(1, S + idx)))
+            scores = scores + (lp * emit).sum(1)
+            m = torch.where(active, m, torch.zeros_like(m))
+            last = torch.where(active, t.gather(1, (m - 1).clamp(min=0)[:, None]).squeeze(1), last)
+            emitted = emitted + m
+            cur = cur + m
+            accepted += (n * active).sum()
+            stats["rounds"] += 1
+            stats["drafted"] += g * B
+        stats["accepted"] = int(accepted.item())
+        if hasattr(drafter, "release"):
+            drafter.release()
+        return out[:, :int(emitted.max().item())], scores
 
     def _device_loop(self, input_ids, lens, logits, cache, max_new, pad, gen):
         """The sampling / greedy loop with the selection on the device

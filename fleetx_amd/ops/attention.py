@@ -380,3 +380,77 @@ def beam_decode_attention(q, kp, vp, plens, kg, vg, glens, anc, scale=None, nspl
     if rc != 0:
         raise NotImplementedError("beam decode attention: unsupported shape (rc %d)" % rc)
     return out
+
+
+WINDOW_KERNEL_MAX = 8  # queries per sample the kernel keeps in registers
+
+
+def window_decode_splits(B, H, maxlen, target_wgs=256, min_chunk=192):
+    """Split-K factor for window decode attention: a function of the cache
+    shape only, never of the lengths, so every call on one cache splits the key
+    axis at the same absolute keys.  The workgroup has the beam kernel's shape
+    (all queries of one (sample, head), 8 waves), so the figures are
+    ``beam_decode_splits``'s, carried over and not measured again."""
+    n = max(1, target_wgs // max(1, B * H))
+    return max(1, min(n, -(-maxlen // min_chunk)))
+
+
+def _window_attention_formula(q, k_cache, v_cache, lens, W, scale):
+    """fp32 math (CPU path, unsupported shapes, test oracle)."""
+    R, H, D = q.shape
+    B, L = k_cache.shape[0], k_cache.shape[1]
+    dev = q.device
+    kf = k_cache.float().repeat_interleave(W, 0)
+    vf = v_cache.float().repeat_interleave(W, 0)
+    s = torch.einsum("rhd,rlhd->rhl", q.float(), kf) * scale
+    lim = lens.to(dev).long().repeat_interleave(W) + torch.arange(W, device=dev).repeat(B)
+    mask = torch.arange(L, device=dev).view(1, L) > lim.view(R, 1)          # [R, L]
+    p = torch.nan_to_num(torch.softmax(s.masked_fill(mask.view(R, 1, L), float("-inf")), -1),
+                         nan=0.0)
+    # masked keys may hold anything (NaN included): 0 * NaN must not reach the sum
+    vf = torch.where(mask.view(R, L, 1, 1), 0.0, vf)
+    return torch.einsum("rhl,rlhd->rhd", p, vf).to(q.dtype)
+
+
+def window_decode_attention(q, k_cache, v_cache, lens, scale=None, nsplit=None, waves=0):
+    """Attention of ``W`` consecutive causal queries per sample over one KV
+    cache (split-K, bf16 / fp16): the verify step of speculative decoding.
+
+    q: [B*W, H, D]; caches: [B, maxlen, H, D]; lens: int32 [B], the number of
+    keys before the window.  The window's own K/V rows are already in the cache
+    at ``lens[b] .. lens[b]+W-1``; row ``b*W + j`` attends to
+    ``k_cache[b, :lens[b] + j + 1]``.  ``lens[b] + W <= maxlen`` is trusted, not
+    checked.  The kernel reads every cache row below ``lens[b] + W`` (they must
+    hold finite values) and none beyond.
+
+    The kernel (1 <= W <= 8, head_dim 64 / 128, GPU tensors) loads each K/V row
+    once for all queries.  A query's result depends on its own ``q`` row and
+    the keys it sees only, not on its slot ``j``.  Anything else runs the fp32
+    formula.  ``waves``: waves per workgroup, 4 or 8 (0: chosen by the number
+    of workgroups).
+    """
+    R, H, D = q.shape
+    B, maxlen = k_cache.shape[0], k_cache.shape[1]
+    if R % B or lens.numel() != B:
+        raise ValueError("window decode attention: q rows must be B*W, lens [B]")
+    W = R // B
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    if not q.is_cuda or W > WINDOW_KERNEL_MAX or D not in (64, 128):
+        return _window_attention_formula(q, k_cache, v_cache, lens, W, scale)
+    dt = _lib.dt_code(q.dtype)
+    if k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
+        raise TypeError("window decode attention: q / cache dtypes differ")
+    if k_cache.stride() != v_cache.stride() or k_cache.stride(-1) != 1 or q.stride(-1) != 1:
+        raise ValueError("window decode attention: caches must share a layout with contiguous "
+                         "head dim")
+    ns = nsplit or window_decode_splits(B, H, maxlen)
+    out = torch.empty(R, H, D, device=q.device, dtype=q.dtype)
+    ws = torch.empty(R * H * ns * (D + 2), device=q.device, dtype=torch.float32)
+    rc = _lib.kernels().window_decode_attn(
+        dt, q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+        lens.to(torch.int32).contiguous().data_ptr(), out.data_ptr(), ws.data_ptr(), B, W, H, D,
+        maxlen, ns, q.stride(0), q.stride(1), k_cache.stride(0), k_cache.stride(1),
+        k_cache.stride(2), out.stride(0), float(scale), int(waves), _lib.stream())
+    if rc != 0:
+        raise NotImplementedError("window decode attention: unsupported shape (rc %d)" % rc)
+    return out

@@ -467,14 +467,21 @@ def _decode_gemv(x, w, wscale, bias, epi, res, qkv_cache, ln, int4=False):
                            or epi not in (GV_GELU, GV_QKV)):
         return None
     k = _lib.kernels()
-    kc = vc = pos = None
+    kc = vc = pos = rows = None
     heads = hd = maxlen = 0
     if epi == GV_QKV:
-        kc, vc, pos = qkv_cache
+        kc, vc, pos = qkv_cache[:3]
+        rows = qkv_cache[3] if len(qkv_cache) > 3 else None
         maxlen, heads, hd = kc.shape[1], kc.shape[2], kc.shape[3]
         assert N == 3 * heads * hd and kc.is_contiguous() and vc.is_contiguous()
-        assert kc.shape == vc.shape and kc.shape[0] >= M and kc.dtype == x.dtype == vc.dtype
+        assert kc.shape == vc.shape and kc.dtype == x.dtype == vc.dtype
         assert pos.dtype == torch.int64 and pos.numel() == M and pos.is_contiguous()
+        if rows is None:
+            assert kc.shape[0] >= M
+        else:
+            # rows.max() < kc.shape[0] is the caller's to keep (no sync to check it)
+            assert rows.dtype == torch.int32 and rows.numel() == M and rows.is_contiguous() \
+                and rows.is_cuda
         y = torch.empty(M, heads * hd, device=x.device, dtype=x.dtype)
     else:
         y = torch.empty(M, N, device=x.device, dtype=x.dtype)
@@ -485,7 +492,7 @@ def _decode_gemv(x, w, wscale, bias, epi, res, qkv_cache, ln, int4=False):
             w.data_ptr(), w.stride(0))
     tail = (_lib.ptr(bias), _lib.ptr(res) if epi == GV_RES else 0,
             res.stride(0) if epi == GV_RES else 0, y.data_ptr(), y.stride(0),
-            _lib.ptr(kc), _lib.ptr(vc), _lib.ptr(pos), heads, hd, maxlen,
+            _lib.ptr(kc), _lib.ptr(vc), _lib.ptr(pos), _lib.ptr(rows), heads, hd, maxlen,
             _lib.ptr(ln[0]) if ln is not None else 0, _lib.ptr(ln[1]) if ln is not None else 0,
             float(ln[2]) if ln is not None else 0.0, _lib.stream())
     if wscale is None:
@@ -505,7 +512,11 @@ def decode_linear(x, weight, bias=None, epi=GV_BIAS, res=None, qkv_cache=None, l
     MFMA GEMV, with the epilogue ``epi``: GV_BIAS (+b), GV_GELU (gelu_tanh(+b)),
     GV_RES (+b + res[M, N]) or GV_QKV (``qkv_cache = (k_cache, v_cache, pos)``:
     the packed [heads][3][head_dim] output is scattered -- q returned as [M, H*D],
-    k/v written into the caches [M, maxlen, H, D] at ``pos`` [M]).
+    k/v written into the caches [M, maxlen, H, D] at ``pos`` [M]; with
+    ``qkv_cache = (k_cache, v_cache, pos, rows)``, ``rows`` int32 [M], row ``m``
+    is written to ``cache[rows[m], pos[m]]``, so one call appends several
+    positions of one sample: the caches are then [B, maxlen, H, D] and
+    ``rows.max() < B`` is trusted, not checked).
 
     ``ln = (weight, bias, eps)`` (GV_GELU / GV_QKV): ``x`` is the residual
     stream and its LayerNorm is fused into the GEMV as a prologue (the

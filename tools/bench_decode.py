@@ -3,13 +3,18 @@
 Prints one JSON line per case: bytes of K+V cache read / kernel time.  The op
 is HBM bound, so the figure of merit is TB/s against the ~8 TB/s peak.
 
-    python tools/bench_decode.py [--dtype bf16|fp16] [--beam-only]
+    python tools/bench_decode.py [--dtype bf16|fp16] [--beam-only] [--window-only]
 
 Beam cases (``"op": "beam"``): ``ops.beam_decode_attention`` (prompt stored
 once per sample, generated slots through the ancestor table) against
 ``ops.decode_attention`` on the same contents expanded to B*nb rows, which is
 the attention of the design that copies the cache per beam.  The per-step index
 copy that design also pays is not included.
+
+Window cases (``"op": "window"``): ``ops.window_decode_attention`` with W
+queries per sample against ONE ``ops.decode_attention`` call on the same B and
+context.  A speculative round replaces W single-query steps by one window
+step, so the figure is how far the window call stays below W single calls.
 """
 import argparse
 import json
@@ -26,10 +31,11 @@ def main():
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--beam-only", action="store_true")
+    ap.add_argument("--window-only", action="store_true")
     a = ap.parse_args()
     from fleetx_amd import ops
     dt = torch.bfloat16 if a.dtype == "bf16" else torch.float16
-    for B, H, D, L in () if a.beam_only else ((1, 32, 128, 32768), (8, 32, 128, 4096), (32, 32, 128, 2048),
+    for B, H, D, L in () if a.beam_only or a.window_only else ((1, 32, 128, 32768), (8, 32, 128, 4096), (32, 32, 128, 2048),
                        (64, 16, 64, 1024), (4, 32, 128, 16384)):
         q = torch.randn(B, H, D, device="cuda", dtype=dt)
         kc = torch.randn(B, L, H, D, device="cuda", dtype=dt)
@@ -53,7 +59,10 @@ def main():
         print(json.dumps({"B": B, "H": H, "D": D, "L": L, "dtype": a.dtype,
                           "nsplit_auto": ops.attention.decode_splits(B, H, L), **res}), flush=True)
         del kc, vc
-    beam_cases(a, dt)
+    if not a.window_only:
+        beam_cases(a, dt)
+    if not a.beam_only:
+        window_cases(a, dt)
 
 
 def _time(fn, iters, reps=20):
@@ -121,6 +130,36 @@ def beam_cases(a, dt):
                                  "TBps": round(bytes_copy / us_copy / 1e6, 3)},
                     "speedup": round(us_copy / us_beam, 2)}), flush=True)
                 del kc, vc
+
+
+def window_cases(a, dt):
+    from fleetx_amd import ops
+    H, D = 32, 128
+    for B in (1, 2):
+        for L in (1024, 4096):
+            kc, vc = (torch.randn(B, L + 8, H, D, device="cuda", dtype=dt) for _ in range(2))
+            lens1 = torch.full((B,), L, device="cuda", dtype=torch.int32)
+            q1 = torch.randn(B, H, D, device="cuda", dtype=dt)
+            us_one = _time(lambda: ops.decode_attention(q1, kc, vc, lens1), a.iters)
+            for W in (2, 5, 8):
+                q = torch.randn(B * W, H, D, device="cuda", dtype=dt)
+                lens = torch.full((B,), L - W, device="cuda", dtype=torch.int32)
+                out = ops.window_decode_attention(q, kc, vc, lens)
+                # the last slot sees L keys: the single-query kernel on the same keys
+                ref = ops.decode_attention(q[W - 1::W].contiguous(), kc, vc, lens1)
+                err = ((out[W - 1::W].float() - ref.float()).norm() / ref.float().norm()).item()
+                us_win = _time(lambda: ops.window_decode_attention(q, kc, vc, lens), a.iters)
+                nbytes = 2 * B * L * H * D * kc.element_size()
+                print(json.dumps({
+                    "op": "window", "B": B, "W": W, "H": H, "D": D, "context": L,
+                    "dtype": a.dtype, "rel_diff": round(err, 5),
+                    "nsplit_window": ops.attention.window_decode_splits(B, H, L + 8),
+                    "nsplit_single": ops.attention.decode_splits(B, H, L + 8),
+                    "window": {"us": round(us_win, 1), "TBps": round(nbytes / us_win / 1e6, 3)},
+                    "single": {"us": round(us_one, 1), "TBps": round(nbytes / us_one / 1e6, 3)},
+                    "window_over_single": round(us_win / us_one, 2),
+                    "W_singles_over_window": round(W * us_one / us_win, 2)}), flush=True)
+            del kc, vc
 
 
 if __name__ == "__main__":

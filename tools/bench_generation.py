@@ -6,6 +6,7 @@ epilogues).  Random-init weights, bf16.
                                      [--strategy beam_search --num-beams 4]
                                      [--weight-quant int8 int4_g256 [--repeat 2]]
                                      [--device-loop [--repeat 3]]
+                                     [--spec-draft int4_g256 --spec-tokens 2 4]
 
 One JSON line per (batch, fused): ms/token, tokens/s and the effective weight
 stream rate (parameter bytes / ms per token).  ``--weight-quant int8`` / ``int4_g256`` (or
@@ -13,7 +14,11 @@ both) adds the weight-only quantised decode paths to every series, alternating
 with the 16-bit one in the same process; ``--repeat`` runs each series that many times (the
 spread of the 16-bit repeats is the yardstick for any difference).
 ``--device-loop`` adds every fused series once more with the token selection
-on the device (``Generation.device_loop``), alternating in the same way."""
+on the device (``Generation.device_loop``), alternating in the same way.
+``--spec-draft`` (greedy search) adds one speculative series per ``--spec-tokens``
+value on the 16-bit target weights, alternating likewise; its lines report ms
+per emitted token, accepted / drafted and the ms of one round (``spec_tokens``
+draft steps and one window step), to put another acceptance rate in."""
 import argparse
 import json
 import os
@@ -41,6 +46,9 @@ def main():
                     help="also run the fused decode on weight-only int8 / int4 copies")
     ap.add_argument("--device-loop", action="store_true",
                     help="also run every fused series with Generation.device_loop")
+    ap.add_argument("--spec-draft", default=None, choices=["int8", "int4_g256"],
+                    help="also run speculative greedy decoding with this draft format")
+    ap.add_argument("--spec-tokens", type=int, nargs="+", default=[4])
     ap.add_argument("--repeat", type=int, default=1)
     args = ap.parse_args()
     from fleetx_amd.models.language_model.gpt.model import GPTConfig, GPTForPretraining
@@ -53,15 +61,19 @@ def main():
     nbytes = sum(p.numel() * p.element_size() for p in model.parameters())
     for B in args.batch:
         prompt = torch.randint(0, 50304, (B, args.prompt), device="cuda")
-        series = [(f, None, False) for f in ((True,) if args.fused_only else (False, True))]
-        series += [(True, wq, False) for wq in args.weight_quant]
+        series = [(f, None, False, 0) for f in ((True,) if args.fused_only else (False, True))]
+        series += [(True, wq, False, 0) for wq in args.weight_quant]
         if args.device_loop and args.strategy != "beam_search":
-            series += [(f, wq, True) for f, wq, _ in series if f]
-        for fused, wq, dloop in series * args.repeat:
-            gen = GPTForGeneration(model, {"max_dec_len": args.tokens, "fused_decode": fused,
-                                           "decode_strategy": args.strategy,
-                                           "num_beams": args.num_beams, "weight_quant": wq,
-                                           "device_loop": dloop})
+            series += [(f, wq, True, 0) for f, wq, _, _ in series if f]
+        if args.spec_draft and args.strategy == "greedy_search":
+            series += [(True, None, False, k) for k in args.spec_tokens]
+        for fused, wq, dloop, spec in series * args.repeat:
+            conf = {"max_dec_len": args.tokens, "fused_decode": fused,
+                    "decode_strategy": args.strategy, "num_beams": args.num_beams,
+                    "weight_quant": wq, "device_loop": dloop}
+            if spec:
+                conf.update(spec_draft=args.spec_draft, spec_tokens=spec)
+            gen = GPTForGeneration(model, conf)
             gen.generate(prompt, max_length=8)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -75,14 +87,24 @@ def main():
             ms = 1e3 * (t - t_pre) / max(1, ids.shape[1] - 1)
             persistent = fused and B <= 4 and \
                 os.environ.get("FLEETX_DECODE_PERSISTENT", "0") == "1"
-            print(json.dumps({"model": args.model, "batch": B, "strategy": args.strategy,
-                              "num_beams": args.num_beams if args.strategy == "beam_search" else 1,
-                              "fused_decode": fused, "weight_quant": wq,
-                              "device_loop": dloop,
-                              "persistent_layers": persistent,
-                              "ms_per_token": round(ms, 3),
-                              "tokens_per_s": round(B * 1e3 / ms, 1),
-                              "weight_TB_s": round(nbytes / (ms * 1e-3) / 1e12, 2)}), flush=True)
+            line = {"model": args.model, "batch": B, "strategy": args.strategy,
+                    "num_beams": args.num_beams if args.strategy == "beam_search" else 1,
+                    "fused_decode": fused, "weight_quant": wq,
+                    "device_loop": dloop,
+                    "persistent_layers": persistent,
+                    "ms_per_token": round(ms, 3),
+                    "tokens_per_s": round(B * 1e3 / ms, 1),
+                    "weight_TB_s": round(nbytes / (ms * 1e-3) / 1e12, 2)}
+            st = gen.last_spec_stats
+            if spec and st:
+                # ms_per_token is per emitted token; the weight rate of a 16-bit
+                # pass per token does not describe a speculative round
+                del line["weight_TB_s"]
+                line.update(spec_draft=args.spec_draft, spec_tokens=spec, rounds=st["rounds"],
+                            accepted=st["accepted"], drafted=st["drafted"],
+                            acceptance=round(st["accepted"] / max(1, st["drafted"]), 3),
+                            ms_per_round=round(1e3 * (t - t_pre) / max(1, st["rounds"]), 3))
+            print(json.dumps(line), flush=True)
 
 
 if __name__ == "__main__":
