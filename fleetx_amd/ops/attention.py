@@ -259,33 +259,55 @@ def decode_attention(q, k_cache, v_cache, lens, scale=None, nsplit=None):
     q: [B, H, D]; caches: [B, maxlen, H, D]; lens: int32 [B] valid lengths.
     """
     B, H, D = q.shape
-    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    scale = _default_scale(scale, D)
     if not q.is_cuda:
         L = k_cache.shape[1]
         s = torch.einsum("bhd,blhd->bhl", q.float(), k_cache.float()) * scale
         m = torch.arange(L, device=q.device).view(1, 1, L) >= lens.view(B, 1, 1).to(q.device)
         p = torch.softmax(s.masked_fill(m, float("-inf")), -1)
         return torch.einsum("bhl,blhd->bhd", p, v_cache.float()).to(q.dtype)
-    dt = _lib.dt_code(q.dtype)
-    if k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
-        raise TypeError("decode attention: q / cache dtypes differ")
-    if k_cache.stride() != v_cache.stride() or k_cache.stride(-1) != 1 or q.stride(-1) != 1:
-        raise ValueError("decode attention: caches must share a layout with contiguous head dim")
     maxlen = k_cache.shape[1]
     ns = nsplit or decode_splits(B, H, maxlen)
-    out = torch.empty(B, H, D, device=q.device, dtype=q.dtype)
-    ws = torch.empty(B * H * ns * (D + 2), device=q.device, dtype=torch.float32)
-    rc = _lib.kernels().decode_attn(dt, q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-                                    out.data_ptr(), lens.to(torch.int32).contiguous().data_ptr(),
-                                    B, H, D, maxlen, ns, ws.data_ptr(), q.stride(0), q.stride(1),
-                                    k_cache.stride(0), k_cache.stride(1), k_cache.stride(2),
-                                    out.stride(0), float(scale), _lib.stream())
+    return _split_k_call(
+        "decode attention", q, [(k_cache, v_cache)], ns,
+        lambda dt, out, ws: _lib.kernels().decode_attn(
+            dt, q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(),
+            lens.to(torch.int32).contiguous().data_ptr(), B, H, D, maxlen, ns, ws.data_ptr(),
+            q.stride(0), q.stride(1), k_cache.stride(0), k_cache.stride(1), k_cache.stride(2),
+            out.stride(0), float(scale), _lib.stream()),
+        unsupported=" supports head_dim 64/128")
+
+
+def _default_scale(scale, D):
+    return scale if scale is not None else 1.0 / math.sqrt(D)
+
+
+def _split_k_call(name, q, kv_pairs, ns, call, caches="caches", unsupported=": unsupported shape"):
+    """The GPU path the three decode attention wrappers share: dtype and layout
+    checks of q ``[R, H, D]`` and the (K, V) cache pairs, ``out`` and the fp32
+    split-K workspace, ``rc = call(dt, out, ws)`` and its error."""
+    dt = _lib.dt_code(q.dtype)
+    for t in (t for pair in kv_pairs for t in pair):
+        if t.dtype != q.dtype:
+            raise TypeError("%s: q / cache dtypes differ" % name)
+    if q.stride(-1) != 1 or any(k.stride() != v.stride() or k.stride(-1) != 1
+                                for k, v in kv_pairs):
+        raise ValueError("%s: %s must share a layout with contiguous head dim" % (name, caches))
+    R, H, D = q.shape
+    out = torch.empty(R, H, D, device=q.device, dtype=q.dtype)
+    ws = torch.empty(R * H * ns * (D + 2), device=q.device, dtype=torch.float32)
+    rc = call(dt, out, ws)
     if rc != 0:
-        raise NotImplementedError("decode attention supports head_dim 64/128 (rc %d)" % rc)
+        raise NotImplementedError("%s%s (rc %d)" % (name, unsupported, rc))
     return out
 
 
 BEAM_KERNEL_MAX = 8  # beams per sample the kernel keeps in registers
+
+
+def _multi_query_splits(B, H, maxlen, target_wgs, min_chunk):
+    n = max(1, target_wgs // max(1, B * H))
+    return max(1, min(n, -(-maxlen // min_chunk)))
 
 
 def beam_decode_splits(B, H, maxlen, target_wgs=256, min_chunk=192):
@@ -295,8 +317,7 @@ def beam_decode_splits(B, H, maxlen, target_wgs=256, min_chunk=192):
     (measured, H 32, D 128, prompts 1024 / 4096: 256 workgroups beat both 128
     and 384 at 4 and 8 beams; every further split also lengthens the serial
     combine pass), at least ``min_chunk`` keys per split."""
-    n = max(1, target_wgs // max(1, B * H))
-    return max(1, min(n, -(-maxlen // min_chunk)))
+    return _multi_query_splits(B, H, maxlen, target_wgs, min_chunk)
 
 
 def _beam_attention_formula(q, kp, vp, plens, kg, vg, glens, anc, scale):
@@ -353,33 +374,25 @@ def beam_decode_attention(q, kp, vp, plens, kg, vg, glens, anc, scale=None, nspl
     if R % B or kg.shape[0] != R or anc.shape != (R, G):
         raise ValueError("beam decode attention: q / kg / anc rows must be B*nb, anc [B*nb, G]")
     nb = R // B
-    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    scale = _default_scale(scale, D)
     if not q.is_cuda or nb > BEAM_KERNEL_MAX or D not in (64, 128):
         return _beam_attention_formula(q, kp, vp, plens, kg, vg, glens, anc, scale)
-    dt = _lib.dt_code(q.dtype)
-    for t in (kp, vp, kg, vg):
-        if t.dtype != q.dtype:
-            raise TypeError("beam decode attention: q / cache dtypes differ")
-    if kp.stride() != vp.stride() or kg.stride() != vg.stride() or kp.stride(-1) != 1 \
-            or kg.stride(-1) != 1 or q.stride(-1) != 1:
-        raise ValueError("beam decode attention: K and V caches must share a layout with "
-                         "contiguous head dim")
-    anc = anc.to(torch.int32)
-    if anc.stride(-1) != 1:
-        anc = anc.contiguous()
     ns = nsplit or beam_decode_splits(B, H, S + G)
-    out = torch.empty(R, H, D, device=q.device, dtype=q.dtype)
-    ws = torch.empty(R * H * ns * (D + 2), device=q.device, dtype=torch.float32)
-    rc = _lib.kernels().beam_decode_attn(
-        dt, q.data_ptr(), kp.data_ptr(), vp.data_ptr(),
-        plens.to(torch.int32).contiguous().data_ptr(),
-        kg.data_ptr(), vg.data_ptr(), glens.to(torch.int32).contiguous().data_ptr(), anc.data_ptr(),
-        out.data_ptr(), ws.data_ptr(), B, nb, H, D, S, G, ns, q.stride(0), q.stride(1),
-        kp.stride(0), kp.stride(1), kp.stride(2), kg.stride(0), kg.stride(1), kg.stride(2),
-        anc.stride(0), out.stride(0), float(scale), int(waves), _lib.stream())
-    if rc != 0:
-        raise NotImplementedError("beam decode attention: unsupported shape (rc %d)" % rc)
-    return out
+
+    def call(dt, out, ws):
+        a = anc.to(torch.int32)
+        if a.stride(-1) != 1:
+            a = a.contiguous()
+        return _lib.kernels().beam_decode_attn(
+            dt, q.data_ptr(), kp.data_ptr(), vp.data_ptr(),
+            plens.to(torch.int32).contiguous().data_ptr(),
+            kg.data_ptr(), vg.data_ptr(), glens.to(torch.int32).contiguous().data_ptr(),
+            a.data_ptr(), out.data_ptr(), ws.data_ptr(), B, nb, H, D, S, G, ns, q.stride(0),
+            q.stride(1), kp.stride(0), kp.stride(1), kp.stride(2), kg.stride(0), kg.stride(1),
+            kg.stride(2), a.stride(0), out.stride(0), float(scale), int(waves), _lib.stream())
+
+    return _split_k_call("beam decode attention", q, [(kp, vp), (kg, vg)], ns, call,
+                         caches="K and V caches")
 
 
 WINDOW_KERNEL_MAX = 8  # queries per sample the kernel keeps in registers
@@ -391,8 +404,7 @@ def window_decode_splits(B, H, maxlen, target_wgs=256, min_chunk=192):
     axis at the same absolute keys.  The workgroup has the beam kernel's shape
     (all queries of one (sample, head), 8 waves), so the figures are
     ``beam_decode_splits``'s, carried over and not measured again."""
-    n = max(1, target_wgs // max(1, B * H))
-    return max(1, min(n, -(-maxlen // min_chunk)))
+    return _multi_query_splits(B, H, maxlen, target_wgs, min_chunk)
 
 
 def _window_attention_formula(q, k_cache, v_cache, lens, W, scale):
@@ -434,23 +446,14 @@ def window_decode_attention(q, k_cache, v_cache, lens, scale=None, nsplit=None, 
     if R % B or lens.numel() != B:
         raise ValueError("window decode attention: q rows must be B*W, lens [B]")
     W = R // B
-    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    scale = _default_scale(scale, D)
     if not q.is_cuda or W > WINDOW_KERNEL_MAX or D not in (64, 128):
         return _window_attention_formula(q, k_cache, v_cache, lens, W, scale)
-    dt = _lib.dt_code(q.dtype)
-    if k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
-        raise TypeError("window decode attention: q / cache dtypes differ")
-    if k_cache.stride() != v_cache.stride() or k_cache.stride(-1) != 1 or q.stride(-1) != 1:
-        raise ValueError("window decode attention: caches must share a layout with contiguous "
-                         "head dim")
     ns = nsplit or window_decode_splits(B, H, maxlen)
-    out = torch.empty(R, H, D, device=q.device, dtype=q.dtype)
-    ws = torch.empty(R * H * ns * (D + 2), device=q.device, dtype=torch.float32)
-    rc = _lib.kernels().window_decode_attn(
-        dt, q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-        lens.to(torch.int32).contiguous().data_ptr(), out.data_ptr(), ws.data_ptr(), B, W, H, D,
-        maxlen, ns, q.stride(0), q.stride(1), k_cache.stride(0), k_cache.stride(1),
-        k_cache.stride(2), out.stride(0), float(scale), int(waves), _lib.stream())
-    if rc != 0:
-        raise NotImplementedError("window decode attention: unsupported shape (rc %d)" % rc)
-    return out
+    return _split_k_call(
+        "window decode attention", q, [(k_cache, v_cache)], ns,
+        lambda dt, out, ws: _lib.kernels().window_decode_attn(
+            dt, q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+            lens.to(torch.int32).contiguous().data_ptr(), out.data_ptr(), ws.data_ptr(), B, W, H,
+            D, maxlen, ns, q.stride(0), q.stride(1), k_cache.stride(0), k_cache.stride(1),
+            k_cache.stride(2), out.stride(0), float(scale), int(waves), _lib.stream()))

@@ -27,7 +27,7 @@ def _case(dtype, D, W, B, H, lens, nan_from):
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("D", [64, 128])
-@pytest.mark.parametrize("W", [1, 2, 3, 5, 8])
+@pytest.mark.parametrize("W", [1, 2, 3, 4, 5, 6, 7, 8])
 @pytest.mark.parametrize("BH", [(2, 4), (2, 32)])
 @pytest.mark.parametrize("first", [0, 1])
 def test_window_decode_attention_kernel(dtype, D, W, BH, first):

@@ -1,4 +1,4 @@
-"""Decode-attention bandwidth microbenchmark (split-K kernel, csrc/kernels/quant_decode.hip).
+"""Decode-attention bandwidth microbenchmark (split-K kernel, csrc/kernels/decode_attn.hip).
 
 Prints one JSON line per case: bytes of K+V cache read / kernel time.  The op
 is HBM bound, so the figure of merit is TB/s against the ~8 TB/s peak.
