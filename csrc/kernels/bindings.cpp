@@ -233,6 +233,19 @@ PYBIND11_MODULE(_kernels, m) {
                      reinterpret_cast<int64_t*>(cur), reinterpret_cast<const int64_t*>(lens),
                      S(st));
   });
+  m.def("spec_verify", [](ptr logits, long ld, int B, int W, int V, int n_steps, int eos, int pad,
+                          int min_len, float pen, float inv_pen, int feos, int feos_step, ptr seen,
+                          int words, ptr step, ptr unfinished, ptr finish_len, ptr scores, ptr out,
+                          ptr nxt, ptr cur, ptr tok, ptr pos, ptr wlens, ptr picks, ptr logp,
+                          ptr rounds, ptr accepted, ptr any_active, ptr st) {
+    auto I = [](ptr p) { return reinterpret_cast<int*>(p); };
+    auto L = [](ptr p) { return reinterpret_cast<int64_t*>(p); };
+    return fx_spec_verify(F(logits), ld, B, W, V, n_steps, eos, pad, min_len, pen, inv_pen, feos,
+                          feos_step, reinterpret_cast<unsigned int*>(seen), words, I(step),
+                          I(unfinished), I(finish_len), F(scores), L(out), L(nxt), L(cur), L(tok),
+                          L(pos), I(wlens), I(picks), F(logp), I(rounds), I(accepted),
+                          I(any_active), S(st));
+  });
   m.def("decode_attn", [](int dt, ptr q, ptr kc, ptr vc, ptr out, ptr lens, int B, int H, int D,
                           int maxlen, int nsplit, ptr ws, long sqb, long sqh, long skb, long sks,
                           long skh, long sob, float scale, ptr st) {

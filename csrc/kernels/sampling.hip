@@ -324,18 +324,67 @@ struct ProcLoad {
   int force;      // forced BOS / EOS: this index gets 0, the rest -1e9 (< 0: off)
   int use_pen;
   float pen, inv_pen;
-  __device__ __forceinline__ float operator()(int i) const {
+  __device__ __forceinline__ bool in_seen(int i) const {
+    return (seen[i >> 5] >> (i & 31)) & 1u;
+  }
+  // `hist(i)`: is token i in the row's history (asked only under a penalty)
+  template <typename H>
+  __device__ __forceinline__ float proc(int i, const H& hist) const {
 #pragma clang fp contract(off)
     if (force >= 0) return i == force ? 0.f : -1e9f;
     float x = lg[i];
     if (i == mask_eos) x = -1e9f;
     // rounded products (never contracted into a consumer's add): bitwise torch's
     // GPU `x * pen` and `x / pen`, the latter being `x * fp32(1 / pen)` there
-    if (use_pen && ((seen[i >> 5] >> (i & 31)) & 1u))
+    if (use_pen && hist(i))
       x = x < 0.f ? x * pen : x * inv_pen;
     return x;
   }
+  __device__ __forceinline__ float operator()(int i) const {
+    return proc(i, [&](int t) { return in_seen(t); });
+  }
 };
+
+// ProcLoad for slot j of a speculative window: the history is the row's bitmap
+// plus the drafts d_1 .. d_j, which are held in registers (a rejected draft
+// must never reach the bitmap).  Unused entries and ids outside the
+// vocabulary are -1 and match no index.
+constexpr int MAXW = 8;  // window slots: spec_tokens + 1
+struct DraftLoad : ProcLoad {
+  int d[MAXW - 1];
+  __device__ __forceinline__ float operator()(int i) const {
+    return proc(i, [&](int t) {
+      bool h = in_seen(t);
+#pragma unroll
+      for (int k = 0; k < MAXW - 1; ++k) h |= d[k] == t;
+      return h;
+    });
+  }
+};
+
+// the greedy pick on load(i): the max, the lowest index that holds it, and
+// lse = m + log(sum exp(x - m)); every thread returns the pick
+template <typename L>
+__device__ __forceinline__ int greedy_row(const L& load, int V, Shared& s, float& lse) {
+  const int tid = threadIdx.x;
+  float m = -INFINITY;
+  for (int i = tid; i < V; i += ST) m = fmaxf(m, load(i));
+  m = block_max(m, s);
+  if (tid == 0) s.pick = V;
+  __syncthreads();
+  float se = 0.f;
+  int first = V;
+  for (int i = tid; i < V; i += ST) {
+    const float x = load(i);
+    se += __expf(x - m);
+    if (x == m) first = min(first, i);
+  }
+  se = block_sum(se, s);
+  if (first < V) atomicMin(&s.pick, first);
+  __syncthreads();
+  lse = m + __logf(se);
+  return s.pick < V ? s.pick : 0;
+}
 
 __global__ __launch_bounds__(ST) void select_kernel(SelectArgs a) {
   __shared__ Shared s;
@@ -362,24 +411,7 @@ __global__ __launch_bounds__(ST) void select_kernel(SelectArgs a) {
       pick = sample_row(load, a.V, a.inv_temp, a.top_k, a.top_p, a.u[(long)step * a.B + row],
                         nullptr, s, lse);
     } else {
-      // max, then sum-exp and the lowest index that holds the max
-      float m = -INFINITY;
-      for (int i = tid; i < a.V; i += ST) m = fmaxf(m, load(i));
-      m = block_max(m, s);
-      if (tid == 0) s.pick = a.V;
-      __syncthreads();
-      float se = 0.f;
-      int first = a.V;
-      for (int i = tid; i < a.V; i += ST) {
-        const float x = load(i);
-        se += __expf(x - m);
-        if (x == m) first = min(first, i);
-      }
-      se = block_sum(se, s);
-      if (first < a.V) atomicMin(&s.pick, first);
-      __syncthreads();
-      pick = s.pick < a.V ? s.pick : 0;
-      lse = m + __logf(se);
+      pick = greedy_row(load, a.V, s, lse);
     }
   }
   if (tid == 0) {
@@ -395,6 +427,128 @@ __global__ __launch_bounds__(ST) void select_kernel(SelectArgs a) {
     a.cur[row] = a.lens[row] + step;
     a.step[row] = step + 1;
   }
+}
+
+// ------------------------------------------------------ speculative verify
+// One round of speculative greedy decoding after the window step, state in
+// device memory: spec_pick_kernel takes the target's greedy pick of every
+// window slot, spec_accept_kernel does the bookkeeping the host loop does
+// between two window steps.  Two launches on one stream, so the second sees
+// all picks without a grid-wide sync; a row's state belongs to one thread.
+struct SpecArgs {
+  const float* logits;      // [B*W, V] fp32, read-only; row b*W + j is slot j of sample b
+  long ld_row;
+  int V, B, W;              // W = spec_tokens + 1 <= MAXW
+  int n_steps;
+  int eos;                  // < 0: none
+  int min_len;              // 0: off
+  int use_pen;
+  float pen, inv_pen;
+  int feos, feos_step;      // forced at step == feos_step (feos < 0: off)
+  unsigned int* seen;       // [B, words]
+  int words;
+  int* step;                // [B] tokens emitted so far (>= 1)
+  int* unfinished;          // [B]
+  int* finish_len;          // [B]
+  float* scores;            // [B]
+  int64_t* out;             // [B, n_steps]
+  int64_t* nxt;             // [B] the last emitted token
+  int64_t* cur;             // [B] its position
+  int64_t* tok;             // [B*W] the window's tokens: nxt, then the drafts d_1 .. d_g
+  int64_t* pos;             // [B*W]
+  int* wlens;               // [B] keys before the window
+  int* picks;               // [B, W]
+  float* logp;              // [B, W]
+  int* rounds;              // [B]
+  int* accepted;            // [B]
+  int* any_active;          // [1]
+};
+
+// Workgroup (b, j): the processed logits of slot j, which chooses token
+// step[b] + j from the history plus the drafts d_1 .. d_j, and their greedy
+// pick.  A row that no longer emits is skipped.  Slots at or past n_steps are
+// picked as well (they are never emitted): the acceptance count covers them,
+// as the host loop's does.
+__global__ __launch_bounds__(ST) void spec_pick_kernel(SpecArgs a) {
+  __shared__ Shared s;
+  const int b = blockIdx.x / a.W, j = blockIdx.x % a.W;
+  const int step = a.step[b];
+  if (!a.unfinished[b] || step >= a.n_steps) return;
+  const int sj = step + j;
+  DraftLoad load;
+  load.lg = a.logits + (long)blockIdx.x * a.ld_row;
+  load.seen = a.seen + (long)b * a.words;
+  load.mask_eos = (a.eos >= 0 && sj < a.min_len) ? a.eos : -1;
+  load.force = (a.feos >= 0 && sj == a.feos_step) ? a.feos : -1;  // step >= 1: never BOS
+  load.use_pen = a.use_pen;
+  load.pen = a.pen;
+  load.inv_pen = a.inv_pen;
+#pragma unroll
+  for (int k = 0; k < MAXW - 1; ++k) {
+    load.d[k] = -1;
+    if (k < j) {
+      const int64_t t = a.tok[(long)b * a.W + 1 + k];
+      if (t >= 0 && t < a.V) load.d[k] = (int)t;
+    }
+  }
+  float lse;
+  const int pick = greedy_row(load, a.V, s, lse);
+  if (threadIdx.x == 0) {
+    a.picks[blockIdx.x] = pick;
+    a.logp[blockIdx.x] = load(pick) - lse;
+  }
+}
+
+// Thread b: accept the longest prefix of row b's drafts that the picks agree
+// with plus the target's next token, cut at n_steps and at the first EOS, and
+// write the next round's window inputs.
+__global__ __launch_bounds__(64) void spec_accept_kernel(SpecArgs a) {
+  const int b = threadIdx.x;
+  int live = 0;
+  if (b < a.B) {
+    const int W = a.W, step = a.step[b];
+    if (a.unfinished[b] && step < a.n_steps) {
+      const int64_t* d = a.tok + (long)b * W;  // d[i] = d_i, i in 1..W-1
+      const int* picks = a.picks + b * W;
+      int n = 0;
+      while (n < W - 1 && d[n + 1] == (int64_t)picks[n]) ++n;
+      int m = min(n + 1, a.n_steps - step);
+      int unf = 1;
+      if (a.eos >= 0) {
+        for (int j = 0; j < m; ++j) {
+          if (picks[j] == a.eos) {
+            m = j + 1;
+            unf = 0;
+            a.unfinished[b] = 0;
+            a.finish_len[b] = step + m;
+            break;
+          }
+        }
+      }
+      unsigned int* seen = a.seen + (long)b * a.words;
+      float sc = a.scores[b];
+      for (int j = 0; j < m; ++j) {
+        const int t = picks[j];  // in [0, V): greedy_row's result
+        a.out[(long)b * a.n_steps + step + j] = t;
+        seen[t >> 5] |= 1u << (t & 31);
+        sc += a.logp[b * W + j];
+      }
+      a.scores[b] = sc;
+      const int64_t last = picks[m - 1];
+      const int64_t cur = a.cur[b] + m;
+      a.nxt[b] = last;
+      a.step[b] = step + m;
+      a.cur[b] = cur;
+      a.rounds[b] += 1;
+      a.accepted[b] += n;
+      a.tok[(long)b * W] = last;
+      for (int j = 0; j < W; ++j) a.pos[(long)b * W + j] = cur + j;
+      a.wlens[b] = (int)cur;
+      live = unf && step + m < a.n_steps;
+    }
+  }
+  const int any = __syncthreads_or(live);
+  if (threadIdx.x == 0) a.any_active[0] = any != 0;
 }
 
 }  // namespace
@@ -435,5 +589,30 @@ extern "C" int fx_select(const float* logits, long ld_row, int B, int V, int sam
   a.finish_len = finish_len, a.scores = scores, a.out = out, a.nxt = nxt, a.cur = cur;
   a.lens = lens;
   select_kernel<<<B, ST, 0, st>>>(a);
+  return 0;
+}
+
+extern "C" int fx_spec_verify(const float* logits, long ld_row, int B, int W, int V, int n_steps,
+                              int eos, int pad, int min_len, float pen, float inv_pen, int feos,
+                              int feos_step, unsigned int* seen, int words, int* step,
+                              int* unfinished, int* finish_len, float* scores, int64_t* out,
+                              int64_t* nxt, int64_t* cur, int64_t* tok, int64_t* pos, int* wlens,
+                              int* picks, float* logp, int* rounds, int* accepted,
+                              int* any_active, hipStream_t st) {
+  if (B <= 0 || V <= 0 || n_steps <= 0) return 0;
+  if (words < (V + 31) / 32) return -1;
+  if (pad < 0 || pad >= V || eos >= V || feos >= V) return -2;
+  if (W < 1 || W > MAXW || B > 64) return -3;
+  SpecArgs a;
+  a.logits = logits, a.ld_row = ld_row, a.V = V, a.B = B, a.W = W, a.n_steps = n_steps;
+  a.eos = eos, a.min_len = min_len;
+  a.use_pen = pen != 1.f, a.pen = pen, a.inv_pen = inv_pen;
+  a.feos = feos, a.feos_step = feos_step;
+  a.seen = seen, a.words = words, a.step = step, a.unfinished = unfinished;
+  a.finish_len = finish_len, a.scores = scores, a.out = out, a.nxt = nxt, a.cur = cur;
+  a.tok = tok, a.pos = pos, a.wlens = wlens, a.picks = picks, a.logp = logp;
+  a.rounds = rounds, a.accepted = accepted, a.any_active = any_active;
+  spec_pick_kernel<<<B * W, ST, 0, st>>>(a);
+  spec_accept_kernel<<<1, 64, 0, st>>>(a);
   return 0;
 }

@@ -24,7 +24,10 @@ MI355X design (K18/K19):
   quantised copies of the model's own weights and verifies ``spec_tokens + 1``
   positions per sample in one window step of the target weights (a cache-row
   map in the QKV GEMV epilogue, ``ops.window_decode_attention``): the target's
-  ids and scores, whatever the drafter proposes.
+  ids and scores, whatever the drafter proposes.  With ``spec_device_loop``
+  the per-slot processors, picks, acceptance and EOS bookkeeping run in two
+  kernels behind the window step (``ops.spec_verify``) and a whole round is
+  one HIP graph replay.
 """
 import os
 import warnings
@@ -449,6 +452,46 @@ class _GraphedDraftStep(_GraphedDecodeStep):
         return logits
 
 
+class _GraphedSpecRound(_GraphedDecodeStep):
+    """One round of speculative decoding with the verify on the device
+    (``spec_device_loop``) as one graph: with the built-in drafter
+    (``draft``) the copy of ``state.nxt`` / ``state.cur`` into the draft
+    step's inputs and ``spec_tokens`` draft steps, each writing its argmax
+    into the window's tokens; then the window step on ``state.tok`` /
+    ``state.pos`` / ``state.wlens`` and ``ops.spec_verify``, which writes the
+    next round's inputs itself.  A round is one replay with no host copy and
+    no host read.  Without ``draft`` (a ``set_drafter`` drafter fills
+    ``state.tok`` from the host) the graph is {window step, verify}."""
+
+    def __init__(self, gen, cache, state, draft):
+        B, W = state.nxt.shape[0], state.window
+        super().__init__(gen, cache, B * W)
+        self.state = state
+        self.nxt, self.cur = state.tok, state.pos
+        self.rows = torch.arange(B, dtype=torch.int32,
+                                 device=state.tok.device).repeat_interleave(W)
+        self.draft = _GraphedDraftStep(gen, cache, B) if draft else None
+
+    def __call__(self):
+        if self.gen.use_hip_graph and self.nxt.is_cuda:
+            self._capture_or_replay()
+        else:
+            self._run()
+
+    def _run(self):
+        st, d = self.state, self.draft
+        if d is not None:
+            d.nxt.copy_(st.nxt)
+            d.cur.copy_(st.cur)
+            tok = st.tok.view(-1, st.window)
+            for i in range(st.window - 1):
+                d._run()
+                tok[:, i + 1].copy_(d.nxt)
+        logits = self.gen._window_step(st.tok, st.pos, self.rows, st.wlens, self.cache)
+        ops.spec_verify(logits, st)
+        return logits
+
+
 class _QuantDrafter:
     """The built-in drafter of speculative decoding: ``k`` greedy decode steps
     on the ``spec_draft`` copies of the model's own weights.  It writes its
@@ -535,6 +578,12 @@ class GPTForGeneration(torch.nn.Module):
             if self.spec_draft == self.weight_quant:
                 raise ValueError("spec_draft must differ from weight_quant (%r): a draft in the "
                                  "target's format saves nothing" % (self.weight_quant,))
+            self._spec_check()
+        # the speculative loop with the verify on the device, one graph replay per round;
+        # any_active is read every spec_poll rounds
+        self.spec_device_loop = bool(c.get("spec_device_loop", False))
+        self.spec_poll = max(1, int(c.get("spec_poll", 1)))
+        if self.spec_device_loop:
             self._spec_check()
         if self.decode_strategy == "beam_search":
             if self.num_beam_groups > 1:
@@ -760,6 +809,8 @@ class GPTForGeneration(torch.nn.Module):
             if not self._device_loop_warned:
                 warnings.warn("device_loop is ignored under tensor parallelism")
                 self._device_loop_warned = True
+        if drafter is not None and self.spec_device_loop:
+            return self._speculative_device(input_ids, lens, logits, cache, max_new, pad, drafter)
         if drafter is not None:
             return self._speculative(input_ids, lens, logits, cache, max_new, pad, total, drafter)
         procs = self._processors(max_new)
@@ -970,6 +1021,48 @@ class GPTForGeneration(torch.nn.Module):
         if hasattr(drafter, "release"):
             drafter.release()
         return out[:, :int(emitted.max().item())], scores
+
+    def _speculative_device(self, input_ids, lens, logits, cache, max_new, pad, drafter):
+        """``_speculative`` with the verify on the device (``spec_device_loop``):
+        token 0 by ``ops.select_token`` on the prefill ``logits``, then rounds
+        of ``_GraphedSpecRound`` on a ``SpecState``.  With the built-in drafter
+        a round is one graph replay; a ``set_drafter`` drafter is asked from
+        the host with the state's device tensors and its tokens are copied
+        into ``state.tok`` before the {window step, verify} graph.  The host
+        reads ``state.any_active`` every ``spec_poll`` rounds and nothing
+        else; a round after every row finished changes no state and writes
+        cache rows below ``total + spec_tokens`` only.  At most ``N - 1``
+        rounds run (every round of an emitting row emits a token).  Ids,
+        scores and ``last_spec_stats`` are those of ``_speculative``."""
+        dev = input_ids.device
+        B = input_ids.shape[0]
+        g = self.spec_tokens
+        N = max(0, min(max_new, self.gpt.cfg.max_position_embeddings - int(lens.max().item())))
+        self.last_spec_stats = {"rounds": 0, "drafted": 0, "accepted": 0}
+        if N == 0:
+            return (torch.zeros(B, 0, dtype=torch.long, device=dev), torch.zeros(B, device=dev))
+        state = ops.SpecState(
+            input_ids, lens, logits.shape[-1], N, g + 1, eos=self.eos_token_id, pad=pad,
+            min_len=self.min_length, penalty=self.repetition_penalty,
+            forced_bos=self.forced_bos_token_id, forced_eos=self.forced_eos_token_id,
+            max_len=max_new)
+        ops.select_token(logits, state)
+        state.start_window()
+        builtin = drafter is self._quant_drafter
+        rnd = _GraphedSpecRound(self, cache, state, builtin)
+        tok = state.tok.view(B, g + 1)
+        for r in range(N - 1):
+            if r % self.spec_poll == 0 and not bool(state.any_active.item()):
+                break
+            if not builtin:
+                tok[:, 1:].copy_(drafter.propose(state.nxt, state.cur, cache, g))
+            rnd()
+        rounds, accepted, T = torch.stack([state.rounds.max().long(), state.accepted.sum(),
+                                           state.finish_len.max().long()]).tolist()
+        self.last_spec_stats = {"rounds": rounds, "drafted": g * B * rounds, "accepted": accepted}
+        if hasattr(drafter, "release"):
+            drafter.release()
+        return state.out[:, :T], state.scores
 
     def _device_loop(self, input_ids, lens, logits, cache, max_new, pad, gen):
         """The sampling / greedy loop with the selection on the device

@@ -8,7 +8,9 @@ reproducible; CPU tensors take the PyTorch reference path
 
 ``select_token`` is the whole per-token selection on the device (logits
 processors, pick, EOS bookkeeping; ``Generation.device_loop``) on a
-``SelectState``.
+``SelectState``.  ``spec_verify`` is the verify step of a speculative greedy
+round (per-slot processors, picks, acceptance, EOS; ``Generation.spec_device_loop``)
+on a ``SpecState``.
 """
 import torch
 
@@ -71,7 +73,13 @@ def _pack_seen(tokens, vocab):
     words = (vocab + 31) // 32
     bits = torch.zeros(B, words * 32, dtype=torch.bool, device=tokens.device)
     bits.scatter_(1, tokens, True)
-    w = (bits.view(B, words, 32).long() << torch.arange(32, device=tokens.device)).sum(-1)
+    return _pack_bits(bits)
+
+
+def _pack_bits(bits):
+    """The bitmap of the boolean set ``bits`` [B, words * 32]."""
+    B = bits.shape[0]
+    w = (bits.view(B, -1, 32).long() << torch.arange(32, device=bits.device)).sum(-1)
     return torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)
 
 
@@ -135,17 +143,20 @@ class SelectState:
         self.cur = self.lens.clone()
 
 
-def processed_logits(logits, state):
+def processed_logits(logits, state, step=None, seen=None):
     """The logits after the processors, as the selection sees them (PyTorch
-    formula; does not change ``state``)."""
+    formula; does not change ``state``).  ``step`` [rows] and ``seen`` bool
+    [rows, V] replace the state's step and history (a window slot of
+    ``spec_verify``: its own step, the history plus its drafts)."""
     st = state
     x = logits.float().clone()
-    step = st.step.long()
+    step = st.step.long() if step is None else step.long()
     if st.min_len and st.eos is not None:
         x[:, st.eos] = torch.where(step < st.min_len, torch.full_like(x[:, 0], -1e9),
                                    x[:, st.eos])
     if st.penalty != 1.0:
-        seen = unpack_seen(st.seen, st.vocab)
+        if seen is None:
+            seen = unpack_seen(st.seen, st.vocab)
         x = torch.where(seen, torch.where(x < 0, x * st.penalty, x / st.penalty), x)
     for tok, at in ((st.forced_bos, 0), (st.forced_eos, st.max_len - 1)):
         if tok is not None:
@@ -231,3 +242,169 @@ def select_token(logits, state):
     st.cur.copy_(torch.where(live, st.lens + step, st.cur))
     st.step += live.int()
     return st.nxt
+
+
+# ---------------------------------------------------------------------------
+# on-device verify of speculative greedy decoding (spec_pick_kernel and
+# spec_accept_kernel in csrc/kernels/sampling.hip)
+# ---------------------------------------------------------------------------
+class SpecState(SelectState):
+    """``SelectState`` of a speculative greedy run (``spec_verify``), greedy
+    only.  ``step`` is the number of tokens emitted, ``nxt`` the last emitted
+    token and ``cur`` its position (it is not in the KV cache yet).  On top of
+    the base state, with ``W = window = spec_tokens + 1``:
+
+    * ``tok`` / ``pos`` int64 [B*W]: the window step's static inputs; row
+      ``b*W`` holds ``nxt[b]``, rows ``b*W + 1 ..`` the round's drafts, which
+      the drafter writes; ``pos[b*W + j] = cur[b] + j``;
+    * ``wlens`` int32 [B]: the keys before the window (``cur``);
+    * ``picks`` int32 [B, W] / ``logp`` fp32 [B, W]: the target's greedy pick
+      of every slot and its log-probability (scratch between the two kernels);
+    * ``rounds`` / ``accepted`` int32 [B]: rounds in which the row still
+      emitted, and the drafts the target agreed with in them;
+    * ``any_active`` int32 [1]: whether any row still emits.
+
+    ``select_token`` on the prefill logits makes token 0; ``start_window``
+    then fills the window inputs."""
+
+    def __init__(self, input_ids, lens, vocab, n_steps, window, **kw):
+        if not 1 <= window <= 8:
+            raise ValueError("window must be in 1..8 (got %r)" % (window,))
+        if input_ids.shape[0] > 64:
+            raise ValueError("spec_verify covers at most 64 rows")
+        super().__init__(input_ids, lens, vocab, n_steps, greedy=True, **kw)
+        dev = input_ids.device
+        B, W = input_ids.shape[0], int(window)
+        self.window = W
+        self.tok = torch.zeros(B * W, dtype=torch.long, device=dev)
+        self.pos = torch.zeros(B * W, dtype=torch.long, device=dev)
+        self.wlens = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.picks = torch.zeros(B, W, dtype=torch.int32, device=dev)
+        self.logp = torch.zeros(B, W, dtype=torch.float32, device=dev)
+        self.rounds = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.accepted = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.any_active = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def active(self):
+        """bool [B]: the rows that still emit."""
+        return (self.unfinished != 0) & (self.step < self.n_steps)
+
+    def start_window(self):
+        """The first round's window inputs, from the state after token 0."""
+        B, W = self.nxt.shape[0], self.window
+        self.tok.view(B, W)[:, 0] = self.nxt
+        self.pos.copy_((self.cur[:, None]
+                        + torch.arange(W, device=self.cur.device)[None, :]).reshape(-1))
+        self.wlens.copy_(self.cur)
+        self.any_active.copy_(self.active().any().to(torch.int32).view(1))
+
+
+def spec_verify(logits, state):
+    """The verify step of one speculative round on the device: ``logits``
+    [B*W, V] fp32 are the window step's (row ``b*W + j`` is slot ``j`` of
+    sample ``b``; not written), the drafts ``d_1 .. d_g`` (``g = W - 1``) are
+    in ``state.tok[b*W + 1 ..]``.  Everything comes from and goes into
+    ``state`` (``SpecState``); nothing is returned or read back, so a whole
+    round can be captured into one HIP graph.
+
+    Per row, if ``unfinished`` and ``step < n_steps`` (any other row is left
+    unchanged):
+
+    * slot ``j`` chooses token ``step + j``: the processors act with that step
+      (min length iff ``step + j < min_len``, forced EOS iff ``step + j ==
+      max_len - 1``, never forced BOS) and the repetition penalty sees
+      ``seen`` plus ``d_1 .. d_j`` (ids outside the vocabulary count as not
+      seen; the bitmap itself is not touched); ``picks[j]`` is the argmax
+      (lowest index among equal maxima), ``logp[j] = x'[pick] - logsumexp(x')``.
+      Slots at or past ``n_steps`` are picked too and never emitted;
+    * ``n`` = the leading ``i`` in ``1..g`` with ``d_i == picks[i-1]``;
+      ``m = min(n + 1, n_steps - step)``; an EOS among ``picks[:m]`` cuts ``m``
+      after its first occurrence, clears ``unfinished`` and sets
+      ``finish_len = step + m``;
+    * for ``j < m``: ``out[step + j] = picks[j]``, ``seen`` gains it,
+      ``scores += logp[j]``;
+    * ``nxt = picks[m-1]``, ``step += m``, ``cur += m``, ``rounds += 1``,
+      ``accepted += n``; the next window's ``tok[b*W] = nxt``,
+      ``pos[b*W + j] = cur + j``, ``wlens = cur``.
+
+    ``any_active[0]`` = whether any row still emits after the round.
+
+    GPU tensors run the two kernels (a missing extension raises); CPU tensors
+    take the PyTorch formula with the same semantics."""
+    st = state
+    B, W, V = st.nxt.shape[0], st.window, st.vocab
+    if logits.dim() != 2 or tuple(logits.shape) != (B * W, V):
+        raise ValueError("spec_verify expects [%d, %d] logits" % (B * W, V))
+    if logits.is_cuda:
+        if logits.dtype != torch.float32 or logits.stride(1) != 1:
+            logits = logits.float().contiguous()
+        none = lambda t: -1 if t is None else int(t)  # noqa: E731
+        rc = _lib.kernels().spec_verify(
+            logits.data_ptr(), logits.stride(0), B, W, V, st.n_steps, none(st.eos), st.pad,
+            st.min_len, st.penalty, st.inv_penalty, none(st.forced_eos), st.max_len - 1,
+            st.seen.data_ptr(), st.seen.shape[1], st.step.data_ptr(), st.unfinished.data_ptr(),
+            st.finish_len.data_ptr(), st.scores.data_ptr(), st.out.data_ptr(), st.nxt.data_ptr(),
+            st.cur.data_ptr(), st.tok.data_ptr(), st.pos.data_ptr(), st.wlens.data_ptr(),
+            st.picks.data_ptr(), st.logp.data_ptr(), st.rounds.data_ptr(),
+            st.accepted.data_ptr(), st.any_active.data_ptr(), _lib.stream())
+        if rc != 0:
+            raise RuntimeError("speculative verify launch failed ({})".format(rc))
+        _lib.maybe_sync()
+        return
+    g = W - 1
+    step = st.step.long()
+    active = st.active()
+    lg = logits.float().view(B, W, V)
+    d = st.tok.view(B, W)[:, 1:]
+    ar = torch.arange(W)
+    rows = torch.arange(B)
+    # ---- the picks: slot j sees the history plus d_1 .. d_j
+    seen = unpack_seen(st.seen, V)
+    t = torch.zeros(B, W, dtype=torch.long)
+    lp = torch.zeros(B, W)
+    for j in range(W):
+        if j:
+            ok = (d[:, j - 1] >= 0) & (d[:, j - 1] < V)
+            seen = seen.clone()
+            seen[rows[ok], d[ok, j - 1]] = True
+        x = processed_logits(lg[:, j], st, step + j, seen)
+        t[:, j] = torch.argmax(x, -1)
+        lp[:, j] = x.gather(1, t[:, j:j + 1]).squeeze(1) - torch.logsumexp(x, -1)
+    st.picks.copy_(torch.where(active[:, None], t.int(), st.picks))
+    st.logp.copy_(torch.where(active[:, None], lp, st.logp))
+    # ---- accept
+    n = (d == t[:, :g]).long().cumprod(1).sum(1)
+    m = torch.minimum(n + 1, st.n_steps - step)
+    m = torch.where(active, m, torch.zeros_like(m))
+    emit = ar[None, :] < m[:, None]
+    if st.eos is not None:
+        hit = emit & (t == st.eos)
+        done = hit.any(1)
+        first = torch.where(hit, ar[None, :], W).min(1).values
+        m = torch.where(done, first + 1, m)
+        emit = ar[None, :] < m[:, None]
+        st.finish_len.copy_(torch.where(done, (step + m).int(), st.finish_len))
+        st.unfinished.copy_(torch.where(done, torch.zeros_like(st.unfinished), st.unfinished))
+    # W slack columns: a window may reach past the last emitted token
+    out = torch.cat([st.out, torch.zeros(B, W, dtype=torch.long)], 1)
+    idx = step[:, None] + ar[None, :]
+    out.scatter_(1, idx, torch.where(emit, t, out.gather(1, idx)))
+    st.out.copy_(out[:, :st.n_steps])
+    bits = torch.zeros(B, st.seen.shape[1] * 32, dtype=torch.bool)
+    bits[:, :V] = unpack_seen(st.seen, V)
+    er, ec = emit.nonzero(as_tuple=True)
+    bits[er, t[er, ec]] = True
+    st.seen.copy_(_pack_bits(bits))
+    for j in range(W):  # in slot order, as the kernel adds
+        st.scores += torch.where(emit[:, j], lp[:, j], torch.zeros_like(lp[:, j]))
+    last = t.gather(1, (m - 1).clamp(min=0)[:, None]).squeeze(1)
+    st.nxt.copy_(torch.where(active, last, st.nxt))
+    st.step += m.int()
+    st.cur += m
+    st.rounds += active.int()
+    st.accepted += torch.where(active, n, torch.zeros_like(n)).int()
+    st.tok.view(B, W)[:, 0] = torch.where(active, st.nxt, st.tok.view(B, W)[:, 0])
+    st.pos.copy_(torch.where(active[:, None], st.cur[:, None] + ar[None, :],
+                             st.pos.view(B, W)).reshape(-1))
+    st.wlens.copy_(torch.where(active, st.cur.int(), st.wlens))
+    st.any_active.copy_(st.active().any().to(torch.int32).view(1))

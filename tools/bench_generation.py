@@ -6,7 +6,8 @@ epilogues).  Random-init weights, bf16.
                                      [--strategy beam_search --num-beams 4]
                                      [--weight-quant int8 int4_g256 [--repeat 2]]
                                      [--device-loop [--repeat 3]]
-                                     [--spec-draft int4_g256 --spec-tokens 2 4]
+                                     [--spec-draft int4_g256 --spec-tokens 2 4
+                                      [--spec-device-loop]]
 
 One JSON line per (batch, fused): ms/token, tokens/s and the effective weight
 stream rate (parameter bytes / ms per token).  ``--weight-quant int8`` / ``int4_g256`` (or
@@ -18,7 +19,9 @@ on the device (``Generation.device_loop``), alternating in the same way.
 ``--spec-draft`` (greedy search) adds one speculative series per ``--spec-tokens``
 value on the 16-bit target weights, alternating likewise; its lines report ms
 per emitted token, accepted / drafted and the ms of one round (``spec_tokens``
-draft steps and one window step), to put another acceptance rate in."""
+draft steps and one window step), to put another acceptance rate in.
+``--spec-device-loop`` adds every speculative series once more with the verify
+on the device (``Generation.spec_device_loop``), alternating likewise."""
 import argparse
 import json
 import os
@@ -49,6 +52,8 @@ def main():
     ap.add_argument("--spec-draft", default=None, choices=["int8", "int4_g256"],
                     help="also run speculative greedy decoding with this draft format")
     ap.add_argument("--spec-tokens", type=int, nargs="+", default=[4])
+    ap.add_argument("--spec-device-loop", action="store_true",
+                    help="also run every speculative series with Generation.spec_device_loop")
     ap.add_argument("--repeat", type=int, default=1)
     args = ap.parse_args()
     from fleetx_amd.models.language_model.gpt.model import GPTConfig, GPTForPretraining
@@ -61,18 +66,21 @@ def main():
     nbytes = sum(p.numel() * p.element_size() for p in model.parameters())
     for B in args.batch:
         prompt = torch.randint(0, 50304, (B, args.prompt), device="cuda")
-        series = [(f, None, False, 0) for f in ((True,) if args.fused_only else (False, True))]
-        series += [(True, wq, False, 0) for wq in args.weight_quant]
+        series = [(f, None, False, 0, False)
+                  for f in ((True,) if args.fused_only else (False, True))]
+        series += [(True, wq, False, 0, False) for wq in args.weight_quant]
         if args.device_loop and args.strategy != "beam_search":
-            series += [(f, wq, True, 0) for f, wq, _, _ in series if f]
+            series += [(f, wq, True, 0, False) for f, wq, _, _, _ in series if f]
         if args.spec_draft and args.strategy == "greedy_search":
-            series += [(True, None, False, k) for k in args.spec_tokens]
-        for fused, wq, dloop, spec in series * args.repeat:
+            for k in args.spec_tokens:
+                series += [(True, None, False, k, sdl)
+                           for sdl in ((False, True) if args.spec_device_loop else (False,))]
+        for fused, wq, dloop, spec, sdl in series * args.repeat:
             conf = {"max_dec_len": args.tokens, "fused_decode": fused,
                     "decode_strategy": args.strategy, "num_beams": args.num_beams,
                     "weight_quant": wq, "device_loop": dloop}
             if spec:
-                conf.update(spec_draft=args.spec_draft, spec_tokens=spec)
+                conf.update(spec_draft=args.spec_draft, spec_tokens=spec, spec_device_loop=sdl)
             gen = GPTForGeneration(model, conf)
             gen.generate(prompt, max_length=8)
             torch.cuda.synchronize()
@@ -100,7 +108,8 @@ def main():
                 # ms_per_token is per emitted token; the weight rate of a 16-bit
                 # pass per token does not describe a speculative round
                 del line["weight_TB_s"]
-                line.update(spec_draft=args.spec_draft, spec_tokens=spec, rounds=st["rounds"],
+                line.update(spec_draft=args.spec_draft, spec_tokens=spec, spec_device_loop=sdl,
+                            rounds=st["rounds"],
                             accepted=st["accepted"], drafted=st["drafted"],
                             acceptance=round(st["accepted"] / max(1, st["drafted"]), 3),
                             ms_per_round=round(1e3 * (t - t_pre) / max(1, st["rounds"]), 3))

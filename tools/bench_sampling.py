@@ -1,8 +1,13 @@
 """Decode-step sampling cost: fused HIP top-k/top-p kernel vs the PyTorch op
 chain (softmax, topk, sort/cumsum/scatter, multinomial, log_softmax).
 
-    python tools/bench_sampling.py [--batch 8 --vocab 50304]
-"""
+    python tools/bench_sampling.py [--batch 8 --vocab 50304] [--spec-verify]
+
+``--spec-verify``: GPU time of one ``ops.spec_verify`` (the verify step of a
+speculative round: ``spec_pick_kernel`` + ``spec_accept_kernel``) under HIP
+graph replay at batch 1 and windows 3 / 5 / 8, next to one ``ops.select_token``
+measured the same way.  The state is reset inside the graph so that every
+replay does the full work (all drafts accepted)."""
 import argparse
 import json
 import os
@@ -26,11 +31,46 @@ def timeit(fn, iters=50):
     return e0.elapsed_time(e1) / iters * 1e3
 
 
+def graph_us(fn, reset, iters=200):
+    """GPU microseconds of ``fn`` per graph replay: (reset + fn) minus reset alone."""
+    def timed(body):
+        body()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            body()
+        return timeit(g.replay, iters)
+    both = timed(lambda: (reset(), fn()))
+    return both - timed(reset)
+
+
+def spec_verify_bench(V):
+    from fleetx_amd import ops
+    n_steps = 64
+    ids, lens = torch.randint(0, V, (1, 128), device="cuda"), torch.tensor([128], device="cuda")
+    sel = ops.SelectState(ids, lens, V, n_steps, penalty=1.3)
+    lg1 = torch.randn(1, V, device="cuda")
+    line = {"vocab": V, "batch": 1, "select_token_us": round(
+        graph_us(lambda: ops.select_token(lg1, sel), lambda: sel.step.fill_(3)), 1)}
+    for W in (3, 5, 8):
+        st = ops.SpecState(ids, lens, V, n_steps, W, penalty=1.3)
+        lg = torch.randn(W, V, device="cuda")
+        slot = torch.arange(W, device="cuda")
+        lg[slot, 7 + slot] = 30.0                                   # slot j picks 7 + j ...
+        st.tok[1:] = 7 + slot[:-1]                                  # ... and every draft is accepted
+        line["spec_verify_w%d_us" % W] = round(
+            graph_us(lambda: ops.spec_verify(lg, st), lambda: st.step.fill_(3)), 1)
+    print(json.dumps(line))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--vocab", type=int, default=50304)
+    ap.add_argument("--spec-verify", action="store_true")
     a = ap.parse_args()
+    if a.spec_verify:
+        return spec_verify_bench(a.vocab)
     from fleetx_amd.ops import fused_sample
     from fleetx_amd.models.language_model.gpt.generation import top_k_filter, top_p_filter
     lg = torch.randn(a.batch, a.vocab, device="cuda") * 3
