@@ -161,11 +161,8 @@ PYBIND11_MODULE(_kernels, m) {
                             reinterpret_cast<const int64_t*>(perm), CP(dout), F(dW), ntok, h,
                             vstart, vsize, S(st));
   });
-  m.def("fa_set_dkdv64", &fx_fa_set_dkdv64);
-  m.def("fa_set_dq64", &fx_fa_set_dq64);
-  m.def("fa_set_dkdv_vreg", &fx_fa_set_dkdv_vreg);
-  m.def("fa_set_stamps", [](ptr p) { return fx_fa_set_stamps(P(p)); });  // lab builds: fwd stamps
-  m.def("fa_lab", &fx_fa_lab);  // 1 in tools/fa_lab builds (lab attention variants)
+  m.def("fa_set_stamps", [](ptr p) { return fx_fa_set_stamps(P(p)); });  // lab builds: stamps
+  m.def("fa_lab", &fx_fa_lab);  // 1 in tools/fa_lab builds (per-wave stamps compiled in)
   m.def("flash_fwd", [](int dt, ptr q, ptr k, ptr v, ptr out, ptr lse, std::vector<long> qs,
                         std::vector<long> ks, std::vector<long> vs, std::vector<long> os,
                         ptr kv_lens, ptr kbias, long kb_stride, int B, int H, int Sq, int Sk, int D,

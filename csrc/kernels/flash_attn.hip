@@ -37,12 +37,6 @@ namespace {
 
 constexpr float LOG2E = 1.4426950408889634f;
 #define FA_DKDV_QT 32  // query rows per dK/dV tile
-#ifndef FA_DKDV_V128_QT
-#define FA_DKDV_V128_QT 32  // query rows per tile of the D = 128 V-in-registers dK/dV pass
-#endif
-#ifndef FA_DKDV64_QT
-#define FA_DKDV64_QT 64  // query rows per tile of the 64-keys-per-wave dK/dV kernel
-#endif
 #ifndef FA_RESCALE_THR
 #define FA_RESCALE_THR 8.0f  // log2 units; 0 = rescale on every growth
 #endif
@@ -697,13 +691,8 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void fa_fwd_kernel(AttnParams P) {
       kld.load(row_of(it + 1), smem + (cur ^ 1) * TB, lane);
       vld.load(row_of(it + 1), smem + 2 * TB + (cur ^ 1) * TB, lane);
     }
-#ifdef FA_EXP_NOMASK  // lab timing experiment: the causal grid with the full tile body
-    fwd_tile<T, D, false, DROP, KB>(P, F, kt, vt, qf, oacc, m_run, lsum, row_of(it), wq0, qi,
-                                    kv_len, b, h, sl2, cb);
-#else
     fwd_tile<T, D, CAUSAL, DROP, KB>(P, F, kt, vt, qf, oacc, m_run, lsum, row_of(it), wq0, qi,
                                      kv_len, b, h, sl2, cb);
-#endif
     FA_ST(3 + 2 * it);
     if (switch_item) {
       finish();
@@ -928,7 +917,6 @@ __device__ __forceinline__ uint32_t dpp_swap1(uint32_t v) {
 // 128-row LDS image (keeps two workgroups per CU at QT = 64).
 template <typename T, int D, bool CAUSAL, bool DROP, bool KB, int QT, bool VREG, int NW = 4>
 __device__ __forceinline__ void dkdv_body(const AttnParams& P, char* smem) {
-  constexpr bool LEAN = D == 128 && VREG;
   constexpr int KR = 32 * NW;  // keys per workgroup
   constexpr int TB = QT * D * 2;
   // one buffer: [Q tile][dO tile][lse2 QT floats][delta QT floats]; then V rows
@@ -1080,57 +1068,17 @@ __device__ __forceinline__ void dkdv_body(const AttnParams& P, char* smem) {
           for (int i = 0; i < 16; ++i)
             if (ki > q0 + crow(i, h)) sacc[i] = -INFINITY;
         }
-        if constexpr (LEAN) {
-          // D = 128 with V in registers: fragments one k-step ahead only (the
-          // compiler would hoist all of them) so the 2-wave budget holds
-          short8 qr = F.row(qt, t, 0), gr = F.row(gt, t, 0);
 #pragma unroll
-          for (int s = 0; s < D / 16; ++s) {
-            asm volatile("" ::: "memory");
-            short8 nq = qr, ng = gr;
-            if (s + 1 < D / 16) {
-              nq = F.row(qt, t, s + 1);
-              ng = F.row(gt, t, s + 1);
-            }
-            sacc = mfma<T>(qr, kf[s], sacc);
-            dpacc = mfma<T>(gr, vf[s], dpacc);
-            qr = nq; gr = ng;
-          }
-        } else {
-#pragma unroll
-          for (int s = 0; s < D / 16; ++s) {
-            sacc = mfma<T>(F.row(qt, t, s), kf[s], sacc);
-            if constexpr (VREG) dpacc = mfma<T>(F.row(gt, t, s), vf[s], dpacc);
-            else dpacc = mfma<T>(F.row(gt, t, s), F.row(vs, w, s), dpacc);
-          }
-        }
-        // LEAN: P o Z and dS of the whole slice to 16-bit before the MFMA
-        // phase, so the fp32 S / dP tiles die first
-        short8 pfa[LEAN ? 2 : 1], dfa[LEAN ? 2 : 1];
-        if constexpr (LEAN) {
-#pragma unroll
-          for (int i = 0; i < 16; ++i) {
-            const int ql_ = 32 * t + crow(i, h);
-            const float p = fexp2(__builtin_fmaf(sacc[i], sl2, kb2 - lse_s[ql_]));
-            if (DROP) {
-              const float z = ((keep >> i) & 1u) ? P.drop_scale : 0.f;
-              pfa[i >> 3][i & 7] = cvt16<T>(p * z);
-              dfa[i >> 3][i & 7] = cvt16<T>(p * (dpacc[i] * z - dl_s[ql_]));
-            } else {
-              pfa[i >> 3][i & 7] = cvt16<T>(p);
-              dfa[i >> 3][i & 7] = cvt16<T>(p * (dpacc[i] - dl_s[ql_]));
-            }
-          }
+        for (int s = 0; s < D / 16; ++s) {
+          sacc = mfma<T>(F.row(qt, t, s), kf[s], sacc);
+          if constexpr (VREG) dpacc = mfma<T>(F.row(gt, t, s), vf[s], dpacc);
+          else dpacc = mfma<T>(F.row(gt, t, s), F.row(vs, w, s), dpacc);
         }
         // P o Z (for dV) and dS (for dK) straight to bf16, one 8-row half at a
         // time: no fp32 copies of the tile stay live across the MFMAs
 #pragma unroll
         for (int ss = 0; ss < 2; ++ss) {
           short8 pf, df;
-          if constexpr (LEAN) {
-            pf = pfa[ss];
-            df = dfa[ss];
-          } else
 #pragma unroll
           for (int j = 0; j < 8; ++j) {
             const int i = 8 * ss + j;
@@ -1177,42 +1125,41 @@ __device__ __forceinline__ void dkdv_body(const AttnParams& P, char* smem) {
   FA_ST2(127);
 }
 
-#ifdef FX_FA_LAB
-#include FX_FA_LAB  // tools/fa_lab/fa_wave64.inc (lab builds only)
-#endif
-
-
+// D = 128: 32-query tiles, the workgroup's V rows in LDS
 template <typename T, int D, bool CAUSAL, bool DROP, bool KB>
 __global__ __launch_bounds__(256, 2) void fa_bwd_dkdv_kernel(AttnParams P) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   dkdv_body<T, D, CAUSAL, DROP, KB, FA_DKDV_QT, false>(P, smem);
 }
+// D <= 96: 64-query tiles, V in registers (D = 128 has no registers for V; it would spill)
 template <typename T, int D, bool CAUSAL, bool DROP, bool KB, int NW = 4>
 __global__ __launch_bounds__(64 * NW, 2) void fa_bwd_dkdv_q64v_kernel(AttnParams P) {
+  static_assert(D <= 96, "V in registers fits the 2-wave budget at D <= 96 only");
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  // launched for D <= 96 only (D = 128 has no registers for V; it would spill)
-  if constexpr (D <= 96) dkdv_body<T, D, CAUSAL, DROP, KB, 64, true, NW>(P, smem);
+  dkdv_body<T, D, CAUSAL, DROP, KB, 64, true, NW>(P, smem);
 }
 
-AttnParams make_params(const void* q, const void* k, const void* v, const long* qs,
-                       const long* ks, const long* vs, int B, int H, int Sq, int Sk, float scale,
-                       float p, uint64_t key, const void* salt) {
-  AttnParams P{};
-  P.q = (const uint16_t*)q;
-  P.k = (const uint16_t*)k;
-  P.v = (const uint16_t*)v;
-  P.sq_b = qs[0]; P.sq_s = qs[1]; P.sq_h = qs[2];
-  P.sk_b = ks[0]; P.sk_s = ks[1]; P.sk_h = ks[2];
-  P.sv_b = vs[0]; P.sv_s = vs[1]; P.sv_h = vs[2];
-  P.B = B; P.H = H; P.Sq = Sq; P.Sk = Sk;
-  P.scale = scale;
-  P.klo = (uint32_t)(key & 0xffffffffu);
-  P.khi = (uint32_t)(key >> 32);
-  P.thr = (uint32_t)(p * 65536.0f + 0.5f);
-  P.drop_scale = p < 1.f ? 1.f / (1.f - p) : 0.f;
-  P.salt = p > 0.f ? reinterpret_cast<const uint64_t*>(salt) : nullptr;
-  return P;
-}
+// The kernels of each pass as one family over <T, D, CAUSAL, DROP, KB, NW>, the
+// form fa_dispatch() takes.
+struct FwdK {
+  template <typename T, int D, bool C, bool R, bool KB, int NW>
+  static auto kernel() { return fa_fwd_kernel<T, D, C, R, KB, NW>; }
+};
+struct DqK {
+  template <typename T, int D, bool C, bool R, bool KB, int NW>
+  static auto kernel() { return fa_bwd_dq_kernel<T, D, C, R, KB, NW>; }
+};
+struct DkdvVregK {
+  template <typename T, int D, bool C, bool R, bool KB, int NW>
+  static auto kernel() { return fa_bwd_dkdv_q64v_kernel<T, D, C, R, KB, NW>; }
+};
+struct DkdvLdsK {
+  template <typename T, int D, bool C, bool R, bool KB, int NW>
+  static auto kernel() {
+    static_assert(NW == 4, "fa_bwd_dkdv_kernel is a 4-wave kernel");
+    return fa_bwd_dkdv_kernel<T, D, C, R, KB>;
+  }
+};
 
 }  // namespace
 
@@ -1226,22 +1173,61 @@ static void fa_launch(void (*kernel)(AttnParams), int grid, size_t smem, hipStre
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), smem, st, P);
 }
 
-// Forward workgroup width: NW waves x 32 queries share one K/V tile stream
-// (FLEETX_FA_FWD_WAVES = 4 or 8; see fwd_waves()).
-template <typename T, int D, int NW>
-static void fa_fwd_dispatch(bool causal, bool drop, bool kbias, int grid, size_t smem,
-                            hipStream_t st, const AttnParams& P) {
-  auto go = [&](void (*k)(AttnParams)) { fa_launch(k, grid, smem, st, P, 64 * NW); };
-  if (causal) {
-    if (drop) go(fa_fwd_kernel<T, D, true, true, false, NW>);
-    else go(fa_fwd_kernel<T, D, true, false, false, NW>);
-  } else if (kbias) {
-    if (drop) go(fa_fwd_kernel<T, D, false, true, true, NW>);
-    else go(fa_fwd_kernel<T, D, false, false, true, NW>);
+// What one pass launches, apart from the kernel: the run-time mode, the grid
+// and the dynamic LDS size.
+struct FaLaunch {
+  bool causal, drop, kbias;
+  int grid;
+  size_t smem;
+  hipStream_t st;
+  const AttnParams& P;
+};
+
+// The six legal (causal, dropout, key bias) instantiations of family K at tile
+// width D with NW waves per workgroup (block size 64 NW).  Key bias is only
+// instantiated for non-causal attention (BERT-style padding masks); causal +
+// bias is rejected by fa_params().
+template <class K, typename T, int D, int NW>
+static void fa_dispatch(const FaLaunch& L) {
+  auto go = [&](void (*k)(AttnParams)) { fa_launch(k, L.grid, L.smem, L.st, L.P, 64 * NW); };
+  if (L.causal) {
+    if (L.drop) go(K::template kernel<T, D, true, true, false, NW>());
+    else go(K::template kernel<T, D, true, false, false, NW>());
+  } else if (L.kbias) {
+    if (L.drop) go(K::template kernel<T, D, false, true, true, NW>());
+    else go(K::template kernel<T, D, false, false, true, NW>());
   } else {
-    if (drop) go(fa_fwd_kernel<T, D, false, true, false, NW>);
-    else go(fa_fwd_kernel<T, D, false, false, false, NW>);
+    if (L.drop) go(K::template kernel<T, D, false, true, false, NW>());
+    else go(K::template kernel<T, D, false, false, false, NW>());
   }
+}
+
+// One row of a launch table: taken when the run-time (tile width, waves) is <D, NW>.
+template <class K, typename T, int D, int NW>
+static bool fa_row(int d, int nw, const FaLaunch& L) {
+  if (d != D || nw != NW) return false;
+  fa_dispatch<K, T, D, NW>(L);
+  return true;
+}
+
+// The launch tables: every (kernel, tile width, waves) the library holds, the
+// rows of "Template coverage" in tests/test_attention_edges_gpu.py.  False:
+// no such kernel (nothing launched).
+template <typename T>
+static bool fa_fwd_rows(int d, int nw, const FaLaunch& L) {
+  return fa_row<FwdK, T, 64, 4>(d, nw, L) || fa_row<FwdK, T, 64, 8>(d, nw, L) ||
+         fa_row<FwdK, T, 96, 3>(d, nw, L) || fa_row<FwdK, T, 96, 4>(d, nw, L) ||
+         fa_row<FwdK, T, 128, 4>(d, nw, L) || fa_row<FwdK, T, 128, 8>(d, nw, L);
+}
+template <typename T>
+static bool fa_dq_rows(int d, int nw, const FaLaunch& L) {
+  return fa_row<DqK, T, 64, 4>(d, nw, L) || fa_row<DqK, T, 96, 3>(d, nw, L) ||
+         fa_row<DqK, T, 96, 4>(d, nw, L) || fa_row<DqK, T, 128, 4>(d, nw, L);
+}
+template <typename T>
+static bool fa_dkdv_rows(int d, int nw, const FaLaunch& L) {
+  return fa_row<DkdvVregK, T, 64, 4>(d, nw, L) || fa_row<DkdvVregK, T, 96, 3>(d, nw, L) ||
+         fa_row<DkdvVregK, T, 96, 4>(d, nw, L) || fa_row<DkdvLdsK, T, 128, 4>(d, nw, L);
 }
 
 static int tile_dim(int d) { return d <= 64 ? 64 : (d <= 96 ? 96 : 128); }
@@ -1266,36 +1252,18 @@ static bool fa_pair_grid() {
 }
 
 #ifdef FX_FA_LAB
-// Lab variants (tools/fa_lab): FLEETX_FA_DKDV64 (dK/dV with 64 keys per wave),
-// FLEETX_FA_DKDV_VREG (D = 128 dK/dV with V in registers), FLEETX_FA_DQ64 (dQ
-// with 64 queries per wave), or the fx_fa_set_* switches (1 on, 0 off, < 0
-// re-reads the environment)
-static int g_dkdv64 = -1, g_dkdv_vreg = -1, g_dq64 = -1;
-static bool lab_flag(int& g, const char* name) {
-  if (g < 0) {
-    const char* e = getenv(name);
-    g = e ? (atoi(e) != 0) : 0;
-  }
-  return g != 0;
-}
-static bool dkdv64() { return lab_flag(g_dkdv64, "FLEETX_FA_DKDV64"); }
-static bool dkdv_vreg() { return lab_flag(g_dkdv_vreg, "FLEETX_FA_DKDV_VREG"); }
-static bool dq64() { return lab_flag(g_dq64, "FLEETX_FA_DQ64"); }
+// Lab build (tools/fa_lab): the per-wave stamps are compiled in
 extern "C" int fx_fa_lab() { return 1; }
-extern "C" void fx_fa_set_dkdv64(int on) { g_dkdv64 = on < 0 ? -1 : (on != 0); }
-extern "C" void fx_fa_set_dkdv_vreg(int on) { g_dkdv_vreg = on < 0 ? -1 : (on != 0); }
-extern "C" void fx_fa_set_dq64(int on) { g_dq64 = on < 0 ? -1 : (on != 0); }
 extern "C" int fx_fa_set_stamps(void* p) {
   return hipMemcpyToSymbol(HIP_SYMBOL(fa_stamps), &p, sizeof(p)) == hipSuccess ? 1 : 0;
 }
 #else
-extern "C" int fx_fa_set_stamps(void*) { return 0; }  // production build: no stamps
-extern "C" int fx_fa_lab() { return 0; }  // production build: no lab variants
-extern "C" void fx_fa_set_dkdv64(int) {}
-extern "C" void fx_fa_set_dkdv_vreg(int) {}
-extern "C" void fx_fa_set_dq64(int) {}
+extern "C" int fx_fa_lab() { return 0; }  // production build: no stamps
+extern "C" int fx_fa_set_stamps(void*) { return 0; }
 #endif
 
+// Forward workgroup width at tile 64 / 128: NW waves x 32 queries share one K/V
+// tile stream (FLEETX_FA_FWD_WAVES = 4 or 8)
 static int fwd_waves() {
   static int nw = [] {
     const char* e = getenv("FLEETX_FA_FWD_WAVES");
@@ -1304,42 +1272,6 @@ static int fwd_waves() {
   }();
   return nw;
 }
-
-#define FA_DISPATCH_D(KERNEL, DD, causal, drop, kbias, grid, smem, st, P)         \
-  do {                                                                          \
-    if (causal) {                                                               \
-      if (drop) fa_launch(KERNEL<T, DD, true, true, false>, grid, smem, st, P); \
-      else fa_launch(KERNEL<T, DD, true, false, false>, grid, smem, st, P);     \
-    } else if (kbias) {                                                         \
-      if (drop) fa_launch(KERNEL<T, DD, false, true, true>, grid, smem, st, P); \
-      else fa_launch(KERNEL<T, DD, false, false, true>, grid, smem, st, P);     \
-    } else {                                                                    \
-      if (drop) fa_launch(KERNEL<T, DD, false, true, false>, grid, smem, st, P); \
-      else fa_launch(KERNEL<T, DD, false, false, false>, grid, smem, st, P);     \
-    }                                                                           \
-  } while (0)
-// one tile width with NW waves per workgroup (block size 64 NW)
-#define FA_DISPATCH_NW(KERNEL, DD, NW, causal, drop, kbias, grid, smem, st, P)                  \
-  do {                                                                                        \
-    if (causal) {                                                                             \
-      if (drop) fa_launch(KERNEL<T, DD, true, true, false, NW>, grid, smem, st, P, 64 * NW);  \
-      else fa_launch(KERNEL<T, DD, true, false, false, NW>, grid, smem, st, P, 64 * NW);      \
-    } else if (kbias) {                                                                       \
-      if (drop) fa_launch(KERNEL<T, DD, false, true, true, NW>, grid, smem, st, P, 64 * NW);  \
-      else fa_launch(KERNEL<T, DD, false, false, true, NW>, grid, smem, st, P, 64 * NW);      \
-    } else {                                                                                  \
-      if (drop) fa_launch(KERNEL<T, DD, false, true, false, NW>, grid, smem, st, P, 64 * NW); \
-      else fa_launch(KERNEL<T, DD, false, false, false, NW>, grid, smem, st, P, 64 * NW);     \
-    }                                                                                         \
-  } while (0)
-// key bias is only instantiated for non-causal attention (BERT-style padding
-// masks); causal + bias is rejected by the launchers.
-#define FA_DISPATCH(KERNEL, D, causal, drop, kbias, grid, smem, st, P)                  \
-  do {                                                                                  \
-    if (D == 128) FA_DISPATCH_D(KERNEL, 128, causal, drop, kbias, grid, smem, st, P);   \
-    else if (D == 96) FA_DISPATCH_D(KERNEL, 96, causal, drop, kbias, grid, smem, st, P); \
-    else FA_DISPATCH_D(KERNEL, 64, causal, drop, kbias, grid, smem, st, P);             \
-  } while (0)
 
 // every output row starts 16-byte aligned (store_row16's 16-byte stores);
 // FLEETX_FA_ROW16=0 forces the 8-byte fallback (tests/test_kernels_gpu.py)
@@ -1350,141 +1282,104 @@ static bool rows16(const void* base, const long* s) {
          s[2] % 8 == 0;
 }
 
-// strides arrays are {batch, seq, head} in elements; head dim contiguous.
-// kbias: optional [B, kb_stride] float additive key bias; kb_stride must be
-// >= round_up(Sk, 128) (tiles read whole 64-key groups).
-template <typename T>
-static int flash_fwd_t(const void* q, const void* k, const void* v, void* out, float* lse,
-                            const long* qs, const long* ks, const long* vs, const long* os,
-                            const int* kv_lens, const float* kbias, long kb_stride, int B, int H,
-                            int Sq, int Sk, int D, int causal, float scale, float p, uint64_t key,
-                            const void* salt, hipStream_t st) {
-  // D is the head dim of the tensors; the kernel runs the smallest tile width
-  // >= D (64 / 96 / 128) with the columns past D read as zeros
+// One call's arguments as the entry points receive them (q / k / v, the
+// mode, the dropout key), checked and turned into the AttnParams fields that
+// forward and backward share.  Strides arrays are {batch, seq, head} in
+// elements; head dim contiguous; o and dout share `os`.  D is the head dim of
+// the tensors; the kernels run the smallest tile width >= D (64 / 96 / 128)
+// with the columns past D read as zeros.  kbias: optional [B, kb_stride] float
+// additive key bias; kb_stride must be >= round_up(Sk, 128) (tiles read whole
+// 64-key groups).  dt: 0 = bf16, 1 = fp16 (inputs, outputs and the MFMA
+// operand type).
+// Returns 0, or the code the entry point returns without a launch: -3 unknown
+// dtype, -1 head dim, -2 key bias with causal or a short bias stride.
+static int fa_params(AttnParams& P, int dt, const void* q, const void* k, const void* v,
+                     const long* qs, const long* ks, const long* vs, const long* os,
+                     const int* kv_lens, const float* kbias, long kb_stride, int B, int H, int Sq,
+                     int Sk, int D, int causal, float scale, float p, uint64_t key,
+                     const void* salt) {
+  if (dt != 0 && dt != 1) return -3;
   if (D % 8 || D <= 0 || D > 128) return -1;
   if (kbias && (causal || kb_stride < ((Sk + 127) / 128) * 128)) return -2;
-  AttnParams P = make_params(q, k, v, qs, ks, vs, B, H, Sq, Sk, scale, p, key, salt);
+  P = AttnParams{};
+  P.q = (const uint16_t*)q;
+  P.k = (const uint16_t*)k;
+  P.v = (const uint16_t*)v;
+  P.sq_b = qs[0]; P.sq_s = qs[1]; P.sq_h = qs[2];
+  P.sk_b = ks[0]; P.sk_s = ks[1]; P.sk_h = ks[2];
+  P.sv_b = vs[0]; P.sv_s = vs[1]; P.sv_h = vs[2];
+  P.so_b = os[0]; P.so_s = os[1]; P.so_h = os[2];
+  P.B = B; P.H = H; P.Sq = Sq; P.Sk = Sk;
   P.dval = D;
-  D = tile_dim(D);
-  P.out = (uint16_t*)out;
-  P.lse = lse;
   P.kv_lens = kv_lens;
   P.kbias = kbias;
   P.kb_b = kb_stride;
-  P.so_b = os[0]; P.so_s = os[1]; P.so_h = os[2];
-  P.row16 = rows16(out, os);
-  const int nw = D == 96 ? waves_for(Sq) : fwd_waves();
-  const int nq = (Sq + 32 * nw - 1) / (32 * nw);
+  P.scale = scale;
+  P.klo = (uint32_t)(key & 0xffffffffu);
+  P.khi = (uint32_t)(key >> 32);
+  P.thr = (uint32_t)(p * 65536.0f + 0.5f);
+  P.drop_scale = p < 1.f ? 1.f / (1.f - p) : 0.f;
+  P.salt = p > 0.f ? reinterpret_cast<const uint64_t*>(salt) : nullptr;
+  return 0;
+}
+
+// Dynamic LDS of the forward and dQ passes: double-buffered 64-key K and V tiles
+static size_t fa_kv_smem(int D) { return 4 * 64 * D * 2; }
+// ... and of the dK/dV pass: double-buffered Q / dO tiles of QT rows with their
+// lse / delta row constants, then `vrows` V rows (0: V in registers)
+static size_t fa_dkdv_smem(int QT, int D, int vrows) {
+  return 2 * (2 * QT * D * 2 + 2 * QT * 4) + vrows * D * 2;
+}
+
+// -4 from a launcher: the table holds no kernel for the geometry (waves_for()
+// and fwd_waves() return no such pair)
+template <typename T>
+static int fa_fwd_launch(AttnParams& P, bool causal, bool drop, hipStream_t st) {
+  const int D = tile_dim(P.dval);
+  const int nw = D == 96 ? waves_for(P.Sq) : fwd_waves();
+  const int nq = (P.Sq + 32 * nw - 1) / (32 * nw);
   P.pair = causal && fa_pair_grid() ? 1 : 0;
-  const int grid = (P.pair ? (nq + 1) / 2 : nq) * B * H;
-  const size_t smem = 4 * 64 * D * 2;
-  const bool drop = p > 0.f, kb = kbias != nullptr;
-  if (nw == 8) {
-    if (D == 128) fa_fwd_dispatch<T, 128, 8>(causal, drop, kb, grid, smem, st, P);
-    else fa_fwd_dispatch<T, 64, 8>(causal, drop, kb, grid, smem, st, P);
-  } else {
-    if (D == 128) fa_fwd_dispatch<T, 128, 4>(causal, drop, kb, grid, smem, st, P);
-    else if (D == 96 && nw == 3) fa_fwd_dispatch<T, 96, 3>(causal, drop, kb, grid, smem, st, P);
-    else if (D == 96) fa_fwd_dispatch<T, 96, 4>(causal, drop, kb, grid, smem, st, P);
-    else fa_fwd_dispatch<T, 64, 4>(causal, drop, kb, grid, smem, st, P);
-  }
-  return 0;
+  const int grid = (P.pair ? (nq + 1) / 2 : nq) * P.B * P.H;
+  const FaLaunch L{causal, drop, P.kbias != nullptr, grid, fa_kv_smem(D), st, P};
+  return fa_fwd_rows<T>(D, nw, L) ? 0 : -4;
 }
 
-// o/dout share strides `os`; dq uses `dqs`; dk/dv share `dks`.
+// dQ first: it also stores delta = rowsum(dO . O), which the dK/dV pass reads.
 template <typename T>
-static int flash_bwd_t(const void* q, const void* k, const void* v, const void* o,
-                            const void* dout, const float* lse, float* delta, void* dq, void* dk,
-                            void* dv, const long* qs, const long* ks, const long* vs,
-                            const long* os, const long* dqs, const long* dks, const int* kv_lens,
-                            const float* kbias, long kb_stride, int B, int H,
-                            int Sq, int Sk, int D, int causal, float scale, float p, uint64_t key,
-                            const void* salt, hipStream_t st) {
-  if (D % 8 || D <= 0 || D > 128) return -1;
-  if (kbias && (causal || kb_stride < ((Sk + 127) / 128) * 128)) return -2;
-  AttnParams P = make_params(q, k, v, qs, ks, vs, B, H, Sq, Sk, scale, p, key, salt);
-  P.dval = D;
-  D = tile_dim(D);
-  P.o = (const uint16_t*)o;
-  P.dout = (const uint16_t*)dout;
-  P.lse = const_cast<float*>(lse);
-  P.delta = delta;
-  P.dq = (uint16_t*)dq;
-  P.dk = (uint16_t*)dk;
-  P.dv = (uint16_t*)dv;
-  P.kv_lens = kv_lens;
-  P.kbias = kbias;
-  P.kb_b = kb_stride;
-  P.so_b = os[0]; P.so_s = os[1]; P.so_h = os[2];
-  P.sdk_b = dks[0]; P.sdk_s = dks[1]; P.sdk_h = dks[2];
-  P.sdq_b = dqs[0]; P.sdq_s = dqs[1]; P.sdq_h = dqs[2];
-  P.row16 = rows16(dq, dqs) && rows16(dk, dks) && rows16(dv, dks);
-  const bool drop = p > 0.f, kb = kbias != nullptr;
-  {
-    const size_t smem = 4 * 64 * D * 2;
-    if (D == 96 && waves_for(Sq) == 3) {
-      const int nq = (Sq + 95) / 96;
-      FA_DISPATCH_NW(fa_bwd_dq_kernel, 96, 3, causal, drop, kb, nq * B * H, smem, st, P);
-#ifdef FX_FA_LAB
-    } else if (D == 128 && dq64()) {
-      FA_DISPATCH_D(fa_bwd_dq64_kernel, 128, causal, drop, kb, (Sq + 255) / 256 * B * H, smem,
-                    st, P);
-#endif
-    } else {
-      const int nq = (Sq + 127) / 128;
-      FA_DISPATCH(fa_bwd_dq_kernel, D, causal, drop, kb, nq * B * H, smem, st, P);
-    }
-  }
-  {
-    // double-buffered Q/dO tiles + row constants, then the WG's V rows
-    // D <= 96: 64-query tiles with V in registers (bwd 0.150 -> 0.144 ms at
-    // B8 S1024 H16 D64, profiles/r3_dkdv/); D = 128 has no 32 VGPRs to spare.
-    const int nk = (Sk + 127) / 128;
-    if (D == 96 && waves_for(Sk) == 3) {
-      const size_t smem = 2 * (2 * 64 * D * 2 + 2 * 64 * 4);
-      FA_DISPATCH_NW(fa_bwd_dkdv_q64v_kernel, 96, 3, causal, drop, kb, (Sk + 95) / 96 * B * H,
-                     smem, st, P);
-    } else if (D <= 96) {
-      const size_t smem = 2 * (2 * 64 * D * 2 + 2 * 64 * 4);
-      FA_DISPATCH(fa_bwd_dkdv_q64v_kernel, D, causal, p > 0.f, kbias != nullptr, nk * B * H,
-                  smem, st, P);
-#ifdef FX_FA_LAB
-    } else if (dkdv_vreg()) {
-      // D = 128, V in registers: no V image in LDS
-      const size_t smem = 2 * (2 * FA_DKDV_V128_QT * D * 2 + 2 * FA_DKDV_V128_QT * 4);
-      FA_DISPATCH_D(fa_bwd_dkdv_v128_kernel, 128, causal, p > 0.f, kbias != nullptr, nk * B * H,
-                    smem, st, P);
-    } else if (dkdv64()) {
-      // 64 keys per wave, one workgroup of 256 keys per CU
-      const size_t smem = 2 * (2 * FA_DKDV64_QT * D * 2 + 2 * FA_DKDV64_QT * 4) + 256 * D * 2;
-      FA_DISPATCH_D(fa_bwd_dkdv_k64_kernel, 128, causal, p > 0.f, kbias != nullptr,
-                    (Sk + 255) / 256 * B * H, smem, st, P);
-#endif
-    } else {
-      const size_t smem = 2 * (2 * FA_DKDV_QT * D * 2 + 2 * FA_DKDV_QT * 4) + 128 * D * 2;
-      FA_DISPATCH(fa_bwd_dkdv_kernel, D, causal, p > 0.f, kbias != nullptr, nk * B * H, smem,
-                  st, P);
-    }
-  }
-  return 0;
+static int fa_bwd_launch(const AttnParams& P, bool causal, bool drop, hipStream_t st) {
+  const int D = tile_dim(P.dval), BH = P.B * P.H;
+  const bool kb = P.kbias != nullptr;
+  const int nwq = D == 96 ? waves_for(P.Sq) : 4;
+  const int nq = (P.Sq + 32 * nwq - 1) / (32 * nwq);
+  if (!fa_dq_rows<T>(D, nwq, FaLaunch{causal, drop, kb, nq * BH, fa_kv_smem(D), st, P}))
+    return -4;
+  // D <= 96: 64-query tiles with V in registers (bwd 0.150 -> 0.144 ms at
+  // B8 S1024 H16 D64, profiles/r3_dkdv/); D = 128 has no 32 VGPRs to spare:
+  // 32-query tiles and the workgroup's 128 V rows in LDS.
+  const int nwk = D == 96 ? waves_for(P.Sk) : 4;
+  const int nk = (P.Sk + 32 * nwk - 1) / (32 * nwk);
+  const size_t smem = D <= 96 ? fa_dkdv_smem(64, D, 0) : fa_dkdv_smem(FA_DKDV_QT, D, 128);
+  return fa_dkdv_rows<T>(D, nwk, FaLaunch{causal, drop, kb, nk * BH, smem, st, P}) ? 0 : -4;
 }
 
-// dt: 0 = bf16, 1 = fp16 (inputs, outputs and the MFMA operand type)
 extern "C" int fx_flash_fwd(int dt, const void* q, const void* k, const void* v, void* out,
                             float* lse, const long* qs, const long* ks, const long* vs,
                             const long* os, const int* kv_lens, const float* kbias,
                             long kb_stride, int B, int H, int Sq, int Sk, int D, int causal,
                             float scale, float p, uint64_t key, const void* salt,
                             hipStream_t st) {
-  if (dt == 0)
-    return flash_fwd_t<bf16>(q, k, v, out, lse, qs, ks, vs, os, kv_lens, kbias, kb_stride, B, H,
-                             Sq, Sk, D, causal, scale, p, key, salt, st);
-  if (dt == 1)
-    return flash_fwd_t<f16>(q, k, v, out, lse, qs, ks, vs, os, kv_lens, kbias, kb_stride, B, H,
-                            Sq, Sk, D, causal, scale, p, key, salt, st);
-  return -3;
+  AttnParams P;
+  if (const int rc = fa_params(P, dt, q, k, v, qs, ks, vs, os, kv_lens, kbias, kb_stride, B, H,
+                               Sq, Sk, D, causal, scale, p, key, salt))
+    return rc;
+  P.out = (uint16_t*)out;
+  P.lse = lse;
+  P.row16 = rows16(out, os);
+  return dt == 0 ? fa_fwd_launch<bf16>(P, causal, p > 0.f, st)
+                 : fa_fwd_launch<f16>(P, causal, p > 0.f, st);
 }
 
+// dq uses strides `dqs`; dk / dv share `dks`.
 extern "C" int fx_flash_bwd(int dt, const void* q, const void* k, const void* v, const void* o,
                             const void* dout, const float* lse, float* delta, void* dq, void* dk,
                             void* dv, const long* qs, const long* ks, const long* vs,
@@ -1492,13 +1387,20 @@ extern "C" int fx_flash_bwd(int dt, const void* q, const void* k, const void* v,
                             const float* kbias, long kb_stride, int B, int H, int Sq, int Sk,
                             int D, int causal, float scale, float p, uint64_t key,
                             const void* salt, hipStream_t st) {
-  if (dt == 0)
-    return flash_bwd_t<bf16>(q, k, v, o, dout, lse, delta, dq, dk, dv, qs, ks, vs, os, dqs, dks,
-                             kv_lens, kbias, kb_stride, B, H, Sq, Sk, D, causal, scale, p, key,
-                             salt, st);
-  if (dt == 1)
-    return flash_bwd_t<f16>(q, k, v, o, dout, lse, delta, dq, dk, dv, qs, ks, vs, os, dqs, dks,
-                            kv_lens, kbias, kb_stride, B, H, Sq, Sk, D, causal, scale, p, key,
-                            salt, st);
-  return -3;
+  AttnParams P;
+  if (const int rc = fa_params(P, dt, q, k, v, qs, ks, vs, os, kv_lens, kbias, kb_stride, B, H,
+                               Sq, Sk, D, causal, scale, p, key, salt))
+    return rc;
+  P.o = (const uint16_t*)o;
+  P.dout = (const uint16_t*)dout;
+  P.lse = const_cast<float*>(lse);
+  P.delta = delta;
+  P.dq = (uint16_t*)dq;
+  P.dk = (uint16_t*)dk;
+  P.dv = (uint16_t*)dv;
+  P.sdq_b = dqs[0]; P.sdq_s = dqs[1]; P.sdq_h = dqs[2];
+  P.sdk_b = dks[0]; P.sdk_s = dks[1]; P.sdk_h = dks[2];
+  P.row16 = rows16(dq, dqs) && rows16(dk, dks) && rows16(dv, dks);
+  return dt == 0 ? fa_bwd_launch<bf16>(P, causal, p > 0.f, st)
+                 : fa_bwd_launch<f16>(P, causal, p > 0.f, st);
 }

@@ -54,9 +54,6 @@ void fx_embedding_fwd(int, const int64_t*, const int64_t*, const void*, const vo
                       int, long, long, hipStream_t);
 void fx_embedding_bwd(int, const int64_t*, const void*, float*, int, int, long, long,
                       hipStream_t);
-void fx_fa_set_dkdv64(int);
-void fx_fa_set_dq64(int);
-void fx_fa_set_dkdv_vreg(int);
 int fx_fa_lab();
 int fx_fa_set_stamps(void*);
 int fx_flash_fwd(int, const void*, const void*, const void*, void*, float*, const long*, const long*,

@@ -626,6 +626,51 @@ def test_no_stray_writes(D, dtype, mode):
             dtype, repr(c))
 
 
+def test_rejected_calls_launch_nothing():
+    """The return codes of ``flash_fwd`` / ``flash_bwd``: -1 for a head dim
+    that is no multiple of 8, -2 for a key bias with the causal mask, -3 for an
+    unknown dtype code; and a rejected call launches nothing: every output
+    buffer keeps its sentinel.  The tensors are real (B 1, H 1, S 32, head dim
+    16, a [1, 128] key bias), so even a wrong launch would stay inside memory
+    this test owns."""
+    from fleetx_amd.ops import _lib
+    from fleetx_amd.ops import attention as A
+    from fleetx_amd.parallel import rng
+    K, st = _lib.kernels(), A._strides
+    B, H, S, D = 1, 1, 32, 16
+    q, k, v, g = (torch.randn(B, S, H, D, device=DEV).to(torch.bfloat16) for _ in range(4))
+    kb = torch.zeros(1, 128, device=DEV)
+    o16 = {n: torch.full((B, S, H, D), 3.0, device=DEV, dtype=torch.bfloat16)
+           for n in ("out", "dq", "dk", "dv")}
+    f32 = {n: torch.full((B * H * S,), -7777.0, device=DEV) for n in ("lse", "delta")}
+    out, dq, dk, dv = (o16[n] for n in ("out", "dq", "dk", "dv"))
+    lse, delta = f32["lse"], f32["delta"]
+
+    def fwd(dt, d, causal, bias):
+        return K.flash_fwd(dt, q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
+                           lse.data_ptr(), st(q), st(k), st(v), st(out), 0, _lib.ptr(bias),
+                           bias.shape[1] if bias is not None else 0, B, H, S, S, d, causal,
+                           0.25, 0.0, 1, rng.device_salt_ptr(), _lib.stream())
+
+    def bwd(dt, d, causal, bias):
+        return K.flash_bwd(dt, q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
+                           g.data_ptr(), lse.data_ptr(), delta.data_ptr(), dq.data_ptr(),
+                           dk.data_ptr(), dv.data_ptr(), st(q), st(k), st(v), st(out), st(dq),
+                           st(dk), 0, _lib.ptr(bias), bias.shape[1] if bias is not None else 0,
+                           B, H, S, S, d, causal, 0.25, 0.0, 1, rng.device_salt_ptr(),
+                           _lib.stream())
+
+    for call in (fwd, bwd):
+        assert call(0, 12, 0, None) == -1, call.__name__
+        assert call(0, D, 1, kb) == -2, call.__name__
+        assert call(2, D, 0, None) == -3, call.__name__
+    torch.cuda.synchronize()
+    for n, t in o16.items():
+        assert bool((t == 3.0).all()), "%s written by a rejected call" % n
+    for n, t in f32.items():
+        assert bool((t == -7777.0).all()), "%s written by a rejected call" % n
+
+
 # ------------------------------------------------- per-process switches (children)
 def _child_main(argv):
     """Forward checks (O, lse) in a process whose environment carries one of

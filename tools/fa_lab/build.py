@@ -1,17 +1,14 @@
-"""Lab copy of the kernel library with the opt-in flash-attention backward
-variants compiled in (``tools/fa_lab/fa_wave64.inc``: dK/dV with 64 keys per
-wave, dQ with 64 queries per wave, D = 128 dK/dV with V in registers).  They
-measured 12-50 % slower than the shipped passes (profiles/r5_fa_wave64/), so
-the production ``fleetx_amd/_C/_kernels*.so`` does not contain them.
+"""Lab copy of the kernel library: ``flash_attn.hip`` compiled with
+``-DFX_FA_LAB``, which adds per-wave ``s_memrealtime`` stamps to the forward
+and dK/dV passes (``fa_set_stamps``; read by ``stamp_fwd.py`` /
+``stamp_bwd.py``).  The production ``fleetx_amd/_C/_kernels*.so`` carries no
+stamps.
 
     python tools/fa_lab/build.py            # -> tools/fa_lab/_kernels<EXT>
-    FLEETX_KERNELS_LIB=tools/fa_lab/_kernels<EXT> FLEETX_FA_DKDV64=1 python ...
+    FLEETX_KERNELS_LIB=tools/fa_lab/_kernels<EXT> python tools/fa_lab/stamp_fwd.py
 
-The lab library also carries per-wave ``s_memrealtime`` stamps of the forward
-and dK/dV passes (``fa_set_stamps``; read by ``stamp_fwd.py`` /
-``stamp_bwd.py``).  ``FX_FA_LAB_DEFS="-DNAME ..."`` builds an experiment
-variant named after its defines (e.g. ``-DFA_EXP_NOMASK``: the causal forward
-grid with the full tile body, timing only).
+``FX_FA_LAB_DEFS="-DNAME ..."`` builds an experiment variant named after its
+defines.
 
 Every other object is the production build's (``build/obj``)."""
 import os
@@ -26,15 +23,14 @@ from fleetx_amd import _build as B  # noqa: E402
 def main():
     B.build_kernels()  # production objects up to date
     kdir = os.path.join(B.CSRC, "kernels")
-    inc = os.path.join(HERE, "fa_wave64.inc")
     # FX_FA_LAB_DEFS="-DNAME ...": an experiment build, named after its defines
     defs = os.environ.get("FX_FA_LAB_DEFS", "").split()
     tag = "".join("_" + d[2:].lower() for d in defs)
     obj = os.path.join(HERE, "flash_attn_lab%s.o" % tag)
     src = os.path.join(kdir, "flash_attn.hip")
-    if B._newer(obj, [src, inc]):
+    if B._newer(obj, [src]):
         B._run([B.hipcc(), "-O3", "-std=c++17", "-fPIC", "--offload-arch=" + B.ARCH,
-                "-munsafe-fp-atomics", "-Wno-unused-result", '-DFX_FA_LAB="%s"' % inc]
+                "-munsafe-fp-atomics", "-Wno-unused-result", "-DFX_FA_LAB"]
                + defs + ["-c", src, "-o", obj])
     objs = [os.path.join(B.OBJ, f) for f in sorted(os.listdir(B.OBJ))
             if f.endswith(".o") and f != "flash_attn.hip.o"] + [obj]
