@@ -172,6 +172,16 @@ PYBIND11_MODULE(_kernels, m) {
                         d.data(), reinterpret_cast<const int*>(kv_lens), F(kbias), kb_stride, B, H,
                         Sq, Sk, D, causal, scale, p, key, CP(salt), S(st));
   });
+  m.def("flash_fwd_qoff", [](int dt, ptr q, ptr k, ptr v, ptr out, ptr lse, std::vector<long> qs,
+                             std::vector<long> ks, std::vector<long> vs, std::vector<long> os,
+                             ptr q_starts, ptr kv_lens, int B, int H, int Sq, int Sk, int D,
+                             float scale, ptr st) {
+    auto a = v3(qs), b = v3(ks), c = v3(vs), d = v3(os);
+    return fx_flash_fwd_qoff(dt, CP(q), CP(k), CP(v), P(out), F(lse), a.data(), b.data(),
+                             c.data(), d.data(), reinterpret_cast<const int*>(q_starts),
+                             reinterpret_cast<const int*>(kv_lens), B, H, Sq, Sk, D, scale,
+                             S(st));
+  });
   m.def("flash_bwd", [](int dt, ptr q, ptr k, ptr v, ptr o, ptr dout, ptr lse, ptr delta, ptr dq,
                         ptr dk,
                         ptr dv, std::vector<long> qs, std::vector<long> ks, std::vector<long> vs,

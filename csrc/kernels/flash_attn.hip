@@ -722,6 +722,167 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void fa_fwd_kernel(AttnParams P) {
 }
 
 // ============================================================================
+// forward with a per-sample query offset (prefill over a KV cache): causal, no
+// dropout, no key bias.  Query row i of sample b sits at absolute position
+// p = q_starts[b] + i and sees key j iff j <= p and j < min(kv_lens[b], Sk);
+// rows at or past kv_len see every key below it.  q_starts and kv_lens are
+// read here, never baked into the launch, so a captured call replays.
+//
+// fa_fwd_kernel's structure with the causal coordinates moved by q_start: a
+// block's tile count is ceil(min(kv_len, q_start + (qblock + 1) QB) / 64),
+// and fwd_tile() takes the wave's first POSITION and the lane's position as
+// its causal coordinates (tile skip, half2, mask pass, per-element mask all
+// move with them).  Its only other use of the query coordinate is the
+// wave-valid check `wq0 < P.Sq`, which holds for positions against
+// q_start + Sq: it gets a copy of the parameters with that bound.  Rows are
+// addressed (Q load, O / lse store) by the row index as before.  Block cost
+// stays linear in the block index, so the paired grid keeps equal pair sums.
+// A kernel of its own (own symbol, q_starts as a second argument): the
+// AttnParams layout and every fa_fwd_kernel instantiation stay as they are.
+// ============================================================================
+template <typename T, int D, int NW>
+__global__ __launch_bounds__(64 * NW, 8 / NW) void fa_fwd_qoff_kernel(AttnParams P,
+                                                                     const int* q_starts) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int KV = 64, TB = KV * D * 2, QB = 32 * NW;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, h = lane >> 5;
+  Frag<D> F;
+  F.init(lane);
+  const int nq = (P.Sq + QB - 1) / QB;
+  int bh, qa, qb2 = -1;
+  if (fa_pair_on(P)) {
+    const int npair = (nq + 1) >> 1;
+    const int lid = xcd_remap(blockIdx.x, npair * P.B * P.H);
+    bh = lid / npair;
+    const int p = lid - bh * npair;
+    qa = nq - 1 - p;
+    qb2 = p != qa ? p : -1;
+  } else {
+    int rank;
+    lpt_order(xcd_remap(blockIdx.x, nq * P.B * P.H), nq, P.B * P.H, bh, rank);
+    qa = nq - 1 - rank;
+  }
+  const int b = bh / P.H, hd = bh % P.H;
+
+  const uint16_t* qp = P.q + b * P.sq_b + hd * P.sq_h;
+  const uint16_t* kp = P.k + b * P.sk_b + hd * P.sk_h;
+  const uint16_t* vp = P.v + b * P.sv_b + hd * P.sv_h;
+  const int kv_len = max(0, min(P.Sk, P.kv_lens[b]));
+  const int q0 = q_starts[b];
+  AttnParams PT = P;  // fwd_tile's wave-valid check, in positions
+  PT.Sq = q0 + P.Sq;
+
+  auto load_q = [&](int qblock, short8 (&qf)[D / 16]) {
+    const int r_ = qblock * QB + w * 32 + (lane & 31);
+#pragma unroll
+    for (int s = 0; s < D / 16; ++s) {
+      if (r_ < P.Sq && 16 * s + 8 * h < P.dval)
+        qf[s] = *reinterpret_cast<const short8*>(qp + (long)r_ * P.sq_s + 16 * s + 8 * h);
+      else
+        qf[s] = (short8){0, 0, 0, 0, 0, 0, 0, 0};
+    }
+  };
+  auto tiles_of = [&](int qblock) {
+    return (min(kv_len, q0 + (qblock + 1) * QB) + KV - 1) / KV;
+  };
+
+  int row = qa * QB + w * 32 + (lane & 31);  // this lane's query row
+  int wp0 = q0 + qa * QB + w * 32;           // position of the wave's first row
+  int pi = wp0 + (lane & 31);                // ... and of this lane's row
+  short8 qf[D / 16];
+  load_q(qa, qf);
+  const int ntA = tiles_of(qa);
+  const int ntiles = ntA + (qb2 >= 0 ? tiles_of(qb2) : 0);
+
+  floatx16 oacc[D / 32];
+#pragma unroll
+  for (int dt = 0; dt < D / 32; ++dt)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) oacc[dt][i] = 0.f;
+  float m_run = -INFINITY, lsum = 0.f;
+  const float sl2 = P.scale * LOG2E;
+
+  auto finish = [&]() {
+    const float ltot = lsum + __shfl_xor(lsum, 32, 64);
+    const float inv = ltot > 0.f ? 1.f / ltot : 0.f;
+    if constexpr (D == 128) {
+      store_row16<T, D>(P.out + b * P.so_b + hd * P.so_h + (long)row * P.so_s, oacc, inv, h,
+                        P.dval, P.row16, row < P.Sq);
+      if (row < P.Sq && h == 0)
+        P.lse[(long)bh * P.Sq + row] = ltot > 0.f ? (m_run + log2f(ltot)) * LN2 : INFINITY;
+    } else if (row < P.Sq) {
+      uint16_t* op = P.out + b * P.so_b + hd * P.so_h + (long)row * P.so_s;
+#pragma unroll
+      for (int dt = 0; dt < D / 32; ++dt)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          ushort4 o;
+          o.x = Elt<T>::from_f(oacc[dt][4 * g + 0] * inv);
+          o.y = Elt<T>::from_f(oacc[dt][4 * g + 1] * inv);
+          o.z = Elt<T>::from_f(oacc[dt][4 * g + 2] * inv);
+          o.w = Elt<T>::from_f(oacc[dt][4 * g + 3] * inv);
+          if (dt * 32 + 8 * g + 4 * h < P.dval)
+            *reinterpret_cast<ushort4*>(op + dt * 32 + 8 * g + 4 * h) = o;
+        }
+      if (h == 0)
+        P.lse[(long)bh * P.Sq + row] = ltot > 0.f ? (m_run + log2f(ltot)) * LN2 : INFINITY;
+    }
+  };
+  auto to_item = [&](int qblock) {
+    row = qblock * QB + w * 32 + (lane & 31);
+    wp0 = q0 + qblock * QB + w * 32;
+    pi = wp0 + (lane & 31);
+  };
+
+  // K/V rows are clamped at kv_len (<= Sk) only; the diagonal is per element
+  GldsStream<D, KV, NW> kld, vld;
+  kld.init(kp, P.sk_s, kv_len, w, lane, P.dval);
+  vld.init(vp, P.sv_s, kv_len, w, lane, P.dval);
+  auto row_of = [&](int t) { return (t < ntA ? t : t - ntA) * KV; };
+  if (ntiles > 0) {
+    kld.load(0, smem, lane);
+    vld.load(0, smem + 2 * TB, lane);
+  }
+  glds_wait();
+  __syncthreads();
+
+  short8 qn[D / 16];
+  for (int it = 0; it < ntiles; ++it) {
+    const int cur = it & 1;
+    const char* kt = smem + cur * TB;
+    const char* vt = smem + 2 * TB + cur * TB;
+    const bool more = it + 1 < ntiles;
+    const bool switch_item = qb2 >= 0 && it == ntA - 1;
+    if (switch_item) load_q(qb2, qn);
+    if (more) {
+      kld.load(row_of(it + 1), smem + (cur ^ 1) * TB, lane);
+      vld.load(row_of(it + 1), smem + 2 * TB + (cur ^ 1) * TB, lane);
+    }
+    fwd_tile<T, D, true, false, false>(PT, F, kt, vt, qf, oacc, m_run, lsum, row_of(it), wp0, pi,
+                                       kv_len, b, h, sl2, 0u);
+    if (switch_item) {
+      finish();
+#pragma unroll
+      for (int dt = 0; dt < D / 32; ++dt)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) oacc[dt][i] = 0.f;
+      m_run = -INFINITY;
+      lsum = 0.f;
+#pragma unroll
+      for (int s = 0; s < D / 16; ++s) qf[s] = qn[s];
+      to_item(qb2);
+    }
+    glds_wait();
+    __syncthreads();
+  }
+  if (qb2 >= 0 && ntA == 0) {  // kv_len == 0: no tile switched the items; both rows are empty
+    finish();
+    to_item(qb2);
+  }
+  finish();
+}
+
+// ============================================================================
 // backward dQ: WG = 4 waves x 32 queries; loop over 64-key tiles.
 //   S^T = K.Q^T, dP^T = V.dO^T (queries on lanes), dQ^T += K^T.dS^T
 // ============================================================================
@@ -1344,6 +1505,31 @@ static int fa_fwd_launch(AttnParams& P, bool causal, bool drop, hipStream_t st) 
   return fa_fwd_rows<T>(D, nw, L) ? 0 : -4;
 }
 
+// The query-offset forward: the rows the default forward launcher picks (tile
+// 64 x 4 waves, 96 x 3, 96 x 4, 128 x 4; FLEETX_FA_FWD_WAVES does not apply).
+template <typename T, int D, int NW>
+static bool fa_qoff_row(int d, int nw, int grid, hipStream_t st, const AttnParams& P,
+                        const int* q_starts) {
+  if (d != D || nw != NW) return false;
+  hipLaunchKernelGGL((fa_fwd_qoff_kernel<T, D, NW>), dim3(grid), dim3(64 * NW), fa_kv_smem(D), st,
+                     P, q_starts);
+  return true;
+}
+template <typename T>
+static int fa_fwd_qoff_launch(AttnParams& P, const int* q_starts, hipStream_t st) {
+  const int D = tile_dim(P.dval);
+  const int nw = D == 96 ? waves_for(P.Sq) : 4;
+  const int nq = (P.Sq + 32 * nw - 1) / (32 * nw);
+  P.pair = fa_pair_grid() ? 1 : 0;
+  const int grid = (P.pair ? (nq + 1) / 2 : nq) * P.B * P.H;
+  return fa_qoff_row<T, 64, 4>(D, nw, grid, st, P, q_starts) ||
+                 fa_qoff_row<T, 96, 3>(D, nw, grid, st, P, q_starts) ||
+                 fa_qoff_row<T, 96, 4>(D, nw, grid, st, P, q_starts) ||
+                 fa_qoff_row<T, 128, 4>(D, nw, grid, st, P, q_starts)
+             ? 0
+             : -4;
+}
+
 // dQ first: it also stores delta = rowsum(dO . O), which the dK/dV pass reads.
 template <typename T>
 static int fa_bwd_launch(const AttnParams& P, bool causal, bool drop, hipStream_t st) {
@@ -1377,6 +1563,27 @@ extern "C" int fx_flash_fwd(int dt, const void* q, const void* k, const void* v,
   P.row16 = rows16(out, os);
   return dt == 0 ? fa_fwd_launch<bf16>(P, causal, p > 0.f, st)
                  : fa_fwd_launch<f16>(P, causal, p > 0.f, st);
+}
+
+// Causal forward of Sq query rows per sample that start at position
+// q_starts[b] of a [B, Sk, H, D] K/V cache (fa_fwd_qoff_kernel).  q_starts and
+// kv_lens: int32 [B] device arrays, both required (-5 without them; the other
+// codes are fa_params()'s).  A rejected call launches nothing.
+extern "C" int fx_flash_fwd_qoff(int dt, const void* q, const void* k, const void* v, void* out,
+                                 float* lse, const long* qs, const long* ks, const long* vs,
+                                 const long* os, const int* q_starts, const int* kv_lens, int B,
+                                 int H, int Sq, int Sk, int D, float scale, hipStream_t st) {
+  AttnParams P;
+  if (const int rc = fa_params(P, dt, q, k, v, qs, ks, vs, os, kv_lens, nullptr, 0, B, H, Sq, Sk,
+                               D, 1, scale, 0.f, 0, nullptr))
+    return rc;
+  if (q_starts == nullptr || kv_lens == nullptr) return -5;
+  if (B <= 0 || H <= 0 || Sq <= 0) return 0;  // nothing to compute
+  P.out = (uint16_t*)out;
+  P.lse = lse;
+  P.row16 = rows16(out, os);
+  return dt == 0 ? fa_fwd_qoff_launch<bf16>(P, q_starts, st)
+                 : fa_fwd_qoff_launch<f16>(P, q_starts, st);
 }
 
 // dq uses strides `dqs`; dk / dv share `dks`.

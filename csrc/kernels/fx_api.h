@@ -59,6 +59,9 @@ int fx_fa_set_stamps(void*);
 int fx_flash_fwd(int, const void*, const void*, const void*, void*, float*, const long*, const long*,
                  const long*, const long*, const int*, const float*, long, int, int, int, int, int,
                  int, float, float, uint64_t, const void*, hipStream_t);
+int fx_flash_fwd_qoff(int, const void*, const void*, const void*, void*, float*, const long*,
+                      const long*, const long*, const long*, const int*, const int*, int, int, int,
+                      int, int, float, hipStream_t);
 int fx_flash_bwd(int, const void*, const void*, const void*, const void*, const void*, const float*,
                  float*, void*, void*, void*, const long*, const long*, const long*, const long*,
                  const long*, const long*, const int*, const float*, long, int, int, int, int, int,

@@ -17,6 +17,11 @@ MI355X design (K18/K19):
   reference ``_forward_`` path);
 * per-token attention uses the split-free decode kernel
   (``ops.decode_attention``) that streams the cache once;
+* a prompt longer than ``prefill_chunk`` tokens is prefilled in chunks over
+  the cache, and a ``GenerationSession`` keeps the cache between
+  ``generate()`` calls so a follow-up turn prefills only its new tokens
+  (``ops.prefill_attention``: causal attention of a query block that starts
+  at a per-sample cache offset);
 * beam search (which the reference accepts and then raises on) keeps the
   prompt's K/V once per sample and the beams as an ancestor table
   (``BeamKVCache``, ``ops.beam_decode_attention``): a reorder moves no K/V;
@@ -237,6 +242,81 @@ def _layer_prefill(layer, x, cache, li, lens):
     x2, h2 = ops.add_layer_norm(a, ab, x, layer.ln2.weight, layer.ln2.bias, layer.ln2.eps)
     m, mb = layer.mlp(h2)
     return ops.bias_dropout_add(m, mb, x2)
+
+
+def _layer_prefill_at(layer, x, cache, li, q_starts, kv_lens, rows, keep):
+    """A block of new tokens per sample over a cache that holds their
+    predecessors (a prefill chunk, a session turn): x [B, n, h]; token ``i`` of
+    row ``b`` sits at position ``q_starts[b] + i`` and its K/V go to cache row
+    ``rows[b, i]`` (the same number); ``kv_lens`` [B] keys are valid once the
+    block is in.  ``keep``: None, or the (batch, token) index pair of the
+    tokens whose cache row exists (padding tokens past the cache are dropped)."""
+    attn = layer.attn
+    h = layer.ln1(x)
+    qkv = attn.qkv_proj(h)
+    b, s = qkv.shape[0], qkv.shape[1]
+    qkv5 = qkv.view(b, s, attn.heads, 3, attn.head_dim)
+    kc, vc = cache.k[li], cache.v[li]
+    if keep is None:
+        ar = torch.arange(b, device=x.device)[:, None]
+        kc[ar, rows] = qkv5[:, :, :, 1]
+        vc[ar, rows] = qkv5[:, :, :, 2]
+    else:
+        bi, si = keep
+        kc[bi, rows[bi, si]] = qkv5[bi, si, :, 1]
+        vc[bi, rows[bi, si]] = qkv5[bi, si, :, 2]
+    o = ops.prefill_attention(qkv5[:, :, :, 0], kc, vc, q_starts, kv_lens).reshape(b, s, -1)
+    a, ab = attn.out_proj(o)
+    x2, h2 = ops.add_layer_norm(a, ab, x, layer.ln2.weight, layer.ln2.bias, layer.ln2.eps)
+    m, mb = layer.mlp(h2)
+    return ops.bias_dropout_add(m, mb, x2)
+
+
+class GenerationSession:
+    """A conversation kept across ``generate(..., session=)`` calls
+    (``GPTForGeneration.new_session``):
+
+    * ``cache``: a ``KVCache`` of ``max_len`` rows;
+    * ``lens`` [B]: tokens of each row's transcript whose K/V are in the cache;
+    * ``pending`` [B]: the row's last emitted token, which is not in the cache
+      yet (the next turn prefills it first), or -1;
+    * ``tokens`` [B, max_len]: the transcript, ``lens + (pending >= 0)`` tokens
+      per row (``history()`` pads it for the repetition penalty);
+    * ``logits``: the fp32 [B, V] logits of the last prefill, the ones that
+      choose the turn's first token.
+
+    The position of a token is its index in the transcript."""
+
+    def __init__(self, cache, batch_size, device):
+        self.cache, self.batch_size, self.max_len = cache, batch_size, cache.max_len
+        self.lens = torch.zeros(batch_size, dtype=torch.long, device=device)
+        self.pending = torch.full((batch_size,), -1, dtype=torch.long, device=device)
+        self.tokens = torch.zeros(batch_size, cache.max_len, dtype=torch.long, device=device)
+        self.logits = None
+        # host mirrors of lens / pending: the checks of a turn read no device memory
+        self._lens, self._pending = [0] * batch_size, [-1] * batch_size
+
+    def reset(self):
+        """Forget the conversation; the cache rows are reused as they are."""
+        self.lens.zero_()
+        self.pending.fill_(-1)
+        self.tokens.zero_()
+        self.logits = None
+        self._lens, self._pending = [0] * self.batch_size, [-1] * self.batch_size
+
+    def history(self):
+        """The transcript [B, L], L the longest row's length, padded with the
+        row's own first token (a duplicate index that penalises nothing new)."""
+        tl = self.lens + (self.pending >= 0).long()
+        L = max(1, max(n + (p >= 0) for n, p in zip(self._lens, self._pending)))
+        h = self.tokens[:, :L]
+        return torch.where(torch.arange(L, device=h.device)[None, :] < tl[:, None], h, h[:, :1])
+
+    def _put(self, tok, first, count):
+        """tokens[b, first[b] + j] = tok[b, j] for j < count[b]."""
+        valid = torch.arange(tok.shape[1], device=tok.device)[None, :] < count[:, None]
+        bi, ji = valid.nonzero(as_tuple=True)
+        self.tokens[bi, first[bi] + ji] = tok[bi, ji]
 
 
 def _layer_decode(layer, x, cache, li, pos, lens_after, rows=None):
@@ -562,6 +642,12 @@ class GPTForGeneration(torch.nn.Module):
         self._device_loop_warned = False
         if self.decode_strategy not in ("sampling", "greedy_search", "beam_search"):
             raise ValueError("decode_strategy must be sampling, greedy_search or beam_search")
+        # prompts longer than this are prefilled in chunks of this many tokens (0: one pass)
+        self.prefill_chunk = c.get("prefill_chunk", 0)
+        if isinstance(self.prefill_chunk, bool) or not isinstance(self.prefill_chunk, int) \
+                or self.prefill_chunk < 0 or self.prefill_chunk % 64:
+            raise ValueError("prefill_chunk must be 0 or a positive multiple of 64 (got %r)"
+                             % (self.prefill_chunk,))
         # speculative greedy decoding: draft on quantised copies, verify spec_tokens + 1
         # positions in one window step of the target weights
         self.spec_draft = c.get("spec_draft")
@@ -754,11 +840,114 @@ class GPTForGeneration(torch.nn.Module):
             logits = M.gather_from_mp(logits)
         return logits.float()
 
+    # ---- prefill
+    def _prompt_logits(self, input_ids, lens, cache, lens32):
+        """Prefill of the right-padded prompts into an empty ``cache`` and the
+        fp32 logits of each row's last token: in one pass, or, for prompts
+        longer than ``prefill_chunk``, in chunks."""
+        B, S = input_ids.shape
+        dev = input_ids.device
+        if self.prefill_chunk and S > self.prefill_chunk:
+            return self._prefill_at(input_ids, lens, [0] * B, cache)
+        pos = torch.arange(S, device=dev).unsqueeze(0).expand(B, S)
+        x = self.gpt.embeddings(input_ids, pos)
+        for li, layer in enumerate(self.gpt.layers):
+            x = _layer_prefill(layer, x, cache, li, lens32)
+        x = self.gpt.final_ln(x)
+        last = x[torch.arange(B, device=dev), lens - 1]
+        return self._logits(last)
+
+    def _prefill_at(self, tok, count, start, cache):
+        """Prefill ``count[b]`` tokens ``tok[b, :count[b]]`` (right-padded
+        [B, S]) at positions ``start[b] ..`` of a cache that holds each row's
+        first ``start[b]`` tokens (``start``: host list), at most
+        ``prefill_chunk`` tokens at a time (0: all at once).  Chunk ``c`` of
+        row ``b`` starts at ``start[b] + c N`` and sees ``start[b] +
+        min(count[b], (c + 1) N)`` keys; its K/V go to the cache rows of its
+        positions.  Padding tokens are written too where their row exists:
+        above the row's valid length, so never visible before the real token
+        overwrites them.  Returns the fp32 logits [B, V] of each row's last
+        token, taken from the chunk it falls in."""
+        B, S = tok.shape
+        dev = tok.device
+        N = self.prefill_chunk or S
+        nrows = cache.k[0].shape[1]
+        start_t = torch.tensor(start, dtype=torch.long, device=dev)
+        ar = torch.arange(B, device=dev)
+        last_pos = count - 1
+        last = None
+        for c in range(-(-S // N)):
+            n = min(N, S - c * N)
+            q_starts = start_t + c * N
+            kv_lens = (start_t + count.clamp(max=c * N + n)).to(torch.int32)
+            rows = q_starts[:, None] + torch.arange(n, device=dev)[None, :]
+            keep = None
+            if max(start) + c * N + n > nrows:
+                keep = (rows < nrows).nonzero(as_tuple=True)
+            pos = rows.clamp(max=self.gpt.cfg.max_position_embeddings - 1)
+            x = self.gpt.embeddings(tok[:, c * N:c * N + n], pos)
+            q32 = q_starts.to(torch.int32)
+            for li, layer in enumerate(self.gpt.layers):
+                x = _layer_prefill_at(layer, x, cache, li, q32, kv_lens, rows, keep)
+            here = (last_pos >= c * N) & (last_pos < c * N + n)
+            xl = x[ar, (last_pos - c * N).clamp(0, n - 1)]
+            last = xl if last is None else torch.where(here[:, None], xl, last)
+        return self._logits(self.gpt.final_ln(last))
+
+    def new_session(self, batch_size, max_len=None):
+        """A ``GenerationSession`` of ``batch_size`` rows whose cache holds
+        ``min(max_len or max_position_embeddings, max_position_embeddings)``
+        tokens per row; pass it to ``generate(..., session=)`` turn by turn."""
+        mpe = self.gpt.cfg.max_position_embeddings
+        p = next(self.parameters())
+        attn0 = self.gpt.layers[0].attn
+        cache = KVCache(len(self.gpt.layers), batch_size, min(max_len or mpe, mpe), attn0.heads,
+                        attn0.head_dim, p.dtype, p.device)
+        return GenerationSession(cache, batch_size, p.device)
+
+    def _session_turn(self, s, input_ids, lens):
+        """Checks of a session turn (each a ``ValueError`` before anything is
+        launched) and its tokens: ``[pending] + new tokens`` per row,
+        right-padded [B, S'], with their counts (device and host)."""
+        if self.decode_strategy == "beam_search" or self.device_loop or self.spec_device_loop \
+                or self.spec_draft is not None or self._drafter is not None:
+            raise ValueError("a session supports sampling and greedy_search in the host loop "
+                             "only (no beam_search, device_loop or speculative decoding)")
+        if self.num_return_sequences != 1:
+            raise ValueError("a session needs num_return_sequences 1")
+        B, S = input_ids.shape
+        if B != s.batch_size:
+            raise ValueError("batch size %d does not match the session's %d" % (B, s.batch_size))
+        new = [S] * B if lens is None else [int(n) for n in lens.tolist()]
+        if any(n < 0 or n > S for n in new):
+            raise ValueError("lens must lie in 0..%d" % S)
+        count = [n + (p >= 0) for n, p in zip(new, s._pending)]
+        if any(n == 0 for n in count):
+            raise ValueError("a row has neither a pending token nor new tokens")
+        if any(a + n > s.max_len for a, n in zip(s._lens, count)):
+            raise ValueError("the turn's tokens do not fit the session's %d rows" % s.max_len)
+        dev = input_ids.device
+        Sp = max(count)
+        src = torch.cat([s.pending.clamp(min=0)[:, None], input_ids], 1)     # [B, S + 1]
+        idx = torch.arange(Sp, device=dev)[None, :] + (s.pending < 0).long()[:, None]
+        tok = src.gather(1, idx.clamp(max=S))
+        return tok, torch.tensor(count, dtype=torch.long, device=dev), count
+
     @torch.no_grad()
-    def generate(self, input_ids, lens=None, max_length=None, seed=None):
+    def generate(self, input_ids, lens=None, max_length=None, seed=None, session=None):
         """input_ids: [B, S] right-padded; lens: [B] prompt lengths.
         Returns (generated ids [B, T], scores [B]); with ``decode_strategy:
         beam_search`` see ``_beam_search``.
+
+        With ``session`` (``new_session``) the call is one turn of a
+        conversation: ``input_ids`` / ``lens`` are the turn's new tokens, only
+        ``[pending] + new tokens`` of each row are prefilled, at offset
+        ``session.lens`` over the session's cache (``ops.prefill_attention``),
+        and the decode runs at the transcript's positions.  Afterwards a row
+        that emitted ``n`` tokens (up to and including its EOS, pads excluded)
+        has ``lens`` grown by the prefilled tokens plus ``n - 1`` and the
+        ``n``-th token pending (``n = 0``: nothing pending).  Sampling and
+        greedy search in the host loop only.
 
         With ``device_loop`` (sampling / greedy only) the processors, the pick
         and the EOS bookkeeping run in one kernel behind the decode step
@@ -769,6 +958,8 @@ class GPTForGeneration(torch.nn.Module):
         CPU an inverse-CDF draw instead of ``torch.multinomial``), so a seed
         does not give the default loop's tokens."""
         self.eval()
+        if session is not None:
+            return self._generate_turn(session, input_ids, lens, max_length, seed)
         self._w8_refresh()  # before the prefill and any graph capture
         if self.decode_strategy == "beam_search":
             return self._beam_search(input_ids, lens, max_length)
@@ -794,13 +985,7 @@ class GPTForGeneration(torch.nn.Module):
             gen = torch.Generator(device=dev)
             gen.manual_seed(seed)
         # ---- prefill
-        pos = torch.arange(S, device=dev).unsqueeze(0).expand(B, S)
-        x = self.gpt.embeddings(input_ids, pos)
-        for li, layer in enumerate(self.gpt.layers):
-            x = _layer_prefill(layer, x, cache, li, lens.to(torch.int32))
-        x = self.gpt.final_ln(x)
-        last = x[torch.arange(B, device=dev), lens - 1]
-        logits = self._logits(last)
+        logits = self._prompt_logits(input_ids, lens, cache, lens.to(torch.int32))
         eos = self.eos_token_id
         pad = self.pad_token_id if self.pad_token_id is not None else (eos if eos is not None else 0)
         if self.device_loop:
@@ -813,12 +998,71 @@ class GPTForGeneration(torch.nn.Module):
             return self._speculative_device(input_ids, lens, logits, cache, max_new, pad, drafter)
         if drafter is not None:
             return self._speculative(input_ids, lens, logits, cache, max_new, pad, total, drafter)
+        out_tokens, scores, _ = self._host_loop(logits, input_ids.clone(), lens.clone(), cache,
+                                                total, max_new, pad, gen)
+        if not out_tokens:
+            return torch.zeros(B, 0, dtype=torch.long, device=dev), scores
+        return torch.stack(out_tokens, 1), scores
+
+    def _generate_turn(self, s, input_ids, lens, max_length, seed):
+        """``generate()`` with a session: see there."""
+        tok, count, hcount = self._session_turn(s, input_ids, lens)   # raises before any launch
+        self._w8_refresh()
+        dev = input_ids.device
+        B = s.batch_size
+        max_new = max_length or self.max_length
+        gen = None
+        if seed is not None:
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(seed)
+        start = list(s._lens)
+        Sp = tok.shape[1]
+        if not any(start) and not (self.prefill_chunk and Sp > self.prefill_chunk):
+            # a first turn in one pass: the plain prefill
+            logits = self._prompt_logits(tok, count, s.cache, count.to(torch.int32))
+        else:
+            logits = self._prefill_at(tok, count, start, s.cache)
+        s.logits = logits.clone()  # the processors write in place
+        s._put(tok, s.lens, count)
+        cur = s.lens + count
+        end = [a + n for a, n in zip(start, hcount)]
+        s.lens.copy_(cur)
+        s.pending.fill_(-1)
+        s._lens, s._pending = end, [-1] * B
+        eos = self.eos_token_id
+        pad = self.pad_token_id if self.pad_token_id is not None else (eos if eos is not None else 0)
+        total = min(max(end) + max_new, s.max_len)
+        out_tokens, scores, emitted = self._host_loop(logits, s.history(), cur.clone(), s.cache,
+                                                      total, max_new, pad, gen, count=True)
+        if not out_tokens:
+            return torch.zeros(B, 0, dtype=torch.long, device=dev), scores
+        out = torch.stack(out_tokens, 1)
+        # a row that emitted n tokens: n - 1 of them are in the cache, the n-th is pending
+        s._put(out, cur, emitted)
+        pending = torch.where(emitted > 0,
+                              out.gather(1, (emitted - 1).clamp(min=0)[:, None]).squeeze(1),
+                              torch.full_like(emitted, -1))
+        s.lens.add_((emitted - 1).clamp(min=0))
+        s.pending.copy_(pending)
+        n = emitted.tolist()
+        s._lens = [a + max(k - 1, 0) for a, k in zip(end, n)]
+        s._pending = [int(t) for t in pending.tolist()]
+        return out, scores
+
+    def _host_loop(self, logits, history, cur, cache, total, max_new, pad, gen, count=False):
+        """The sampling / greedy loop on the host: ``logits`` [B, V] choose the
+        first token, ``history`` [B, L] feeds the processors, ``cur`` [B] is
+        the position of the next token, positions stay below ``total``.
+        Returns the list of [B] token tensors, the scores [B] and, with
+        ``count``, the tokens each row emitted (up to and including its EOS)."""
+        B = logits.shape[0]
+        dev = logits.device
+        eos = self.eos_token_id
         procs = self._processors(max_new)
         unfinished = torch.ones(B, dtype=torch.bool, device=dev)
         scores = torch.zeros(B, device=dev)
+        emitted = torch.zeros(B, dtype=torch.long, device=dev) if count else None
         out_tokens = []
-        cur = lens.clone()
-        history = input_ids.clone()
         graphed = None
         for step in range(max_new):
             if cur.max().item() >= total:
@@ -848,6 +1092,8 @@ class GPTForGeneration(torch.nn.Module):
                 step_score = logp.gather(1, nxt[:, None]).squeeze(1)
             nxt = torch.where(unfinished, nxt, torch.full_like(nxt, pad))
             scores = torch.where(unfinished, scores + step_score, scores)
+            if count:
+                emitted += unfinished
             out_tokens.append(nxt)
             history = torch.cat([history, nxt[:, None]], 1)
             if eos is not None:
@@ -861,9 +1107,7 @@ class GPTForGeneration(torch.nn.Module):
             logits = graphed(nxt, cur) if graphed is not None else \
                 self._decode_step(nxt, cur, cache)
             cur = cur + 1
-        if not out_tokens:
-            return torch.zeros(B, 0, dtype=torch.long, device=dev), scores
-        return torch.stack(out_tokens, 1), scores
+        return out_tokens, scores, emitted
 
     # ---- speculative greedy decoding (spec_draft / set_drafter)
     def _spec_drafter(self, batch, dev):
@@ -1151,12 +1395,7 @@ class GPTForGeneration(torch.nn.Module):
                             p.dtype, dev)
         cache.plens.copy_(lens)
         # ---- prefill on the B prompts
-        pos = torch.arange(S, device=dev).unsqueeze(0).expand(B, S)
-        x = self.gpt.embeddings(input_ids, pos)
-        for li, layer in enumerate(self.gpt.layers):
-            x = _layer_prefill(layer, x, cache, li, cache.plens)
-        x = self.gpt.final_ln(x)
-        logits = self._logits(x[torch.arange(B, device=dev), lens - 1])
+        logits = self._prompt_logits(input_ids, lens, cache, cache.plens)
         V = logits.shape[-1]
         procs = self._processors(max_new)
         eos = self.eos_token_id

@@ -181,10 +181,16 @@ class GPTGenerationModule(BasicModule):
         maxlen = max(len(x) for x in inputs)
         return [[pad_id] * (maxlen - len(x)) + list(x) for x in inputs]
 
-    def generate(self, input_text):
-        return self(input_text)
+    def new_session(self, n):
+        """A session of ``n`` conversations (``GPTForGeneration.new_session``)."""
+        return self.model.new_session(n)
 
-    def forward(self, input_text):
+    def generate(self, input_text, session=None):
+        """``session``: continue those conversations with ``input_text`` as
+        the turn's new text (one string per row)."""
+        return self(input_text, session=session)
+
+    def forward(self, input_text, session=None):
         assert self.tokenizer is not None, "generation from text needs tokenizer files"
         texts = [input_text] if isinstance(input_text, str) else list(input_text)
         ids = [self.tokenizer.encode(t) for t in texts]
@@ -193,7 +199,10 @@ class GPTGenerationModule(BasicModule):
         pad = self.tokenizer.eos_token_id
         arr = torch.tensor([x + [pad] * (maxlen - len(x)) for x in ids])
         dev = next(self.model.parameters()).device
-        out, _ = self.model.generate(arr.to(dev), lens.to(dev))
+        if session is not None:
+            out, _ = self.model.generate(arr.to(dev), lens.to(dev), session=session)
+        else:
+            out, _ = self.model.generate(arr.to(dev), lens.to(dev))
         res = []
         for row in out.tolist():
             if pad in row:

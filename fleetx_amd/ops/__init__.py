@@ -2,7 +2,8 @@
 from .norm import add_layer_norm, layer_norm, layer_norm_keep_input, FusedLayerNorm, col_sum  # noqa: F401
 from .elementwise import bias_gelu, bias_dropout_add, dropout  # noqa: F401
 from .attention import (flash_attention, flash_attention_qkvpacked, attention_reference,  # noqa: F401
-                        decode_attention, beam_decode_attention, window_decode_attention)
+                        decode_attention, beam_decode_attention, window_decode_attention,
+                       prefill_attention)
 from .loss_embed import softmax_cross_entropy, embedding  # noqa: F401
 from .quant import fake_quant, quantize_weight_int8, dequantize_weight_int8  # noqa: F401
 from .quant import (quantize_weight_int4, dequantize_weight_int4, pack_int4,  # noqa: F401

@@ -457,3 +457,76 @@ def window_decode_attention(q, k_cache, v_cache, lens, scale=None, nsplit=None, 
             lens.to(torch.int32).contiguous().data_ptr(), out.data_ptr(), ws.data_ptr(), B, W, H,
             D, maxlen, ns, q.stride(0), q.stride(1), k_cache.stride(0), k_cache.stride(1),
             k_cache.stride(2), out.stride(0), float(scale), int(waves), _lib.stream()))
+
+
+def _prefill_attention_formula(q, k_cache, v_cache, q_starts, kv_lens, scale):
+    """fp32 math (CPU path, unsupported head dims, test oracle): O rounded once
+    to q's dtype and the fp32 lse [B, H, Sq]."""
+    B, Sq, H, D = q.shape
+    L = k_cache.shape[1]
+    dev = q.device
+    pos = q_starts.to(dev).long().view(B, 1) + torch.arange(Sq, device=dev).view(1, Sq)
+    kl = kv_lens.to(dev).long().clamp(max=L).view(B, 1, 1)
+    keys = torch.arange(L, device=dev).view(1, 1, L)
+    mask = ((keys > pos.view(B, Sq, 1)) | (keys >= kl)).view(B, 1, Sq, L)
+    s = torch.einsum("bqhd,blhd->bhql", q.float(), k_cache.float()) * scale
+    s = s.masked_fill(mask, float("-inf"))
+    dead = torch.isinf(s.amax(-1))                                          # no visible key
+    p = torch.nan_to_num(torch.softmax(s, -1), nan=0.0)
+    lse = torch.where(dead, torch.full_like(dead, float("inf"), dtype=torch.float32),
+                      torch.logsumexp(s, -1))
+    # keys no row of the sample sees may hold anything (NaN included): 0 * NaN
+    # must not reach the sum.  A key some row sees holds a real token.
+    seen = keys.view(1, L) < torch.minimum(kl.view(B, 1), pos[:, -1:] + 1)
+    vf = torch.where(seen.view(B, L, 1, 1), v_cache.float(), 0.0)
+    return torch.einsum("bhql,blhd->bqhd", p, vf).to(q.dtype), lse
+
+
+def prefill_attention(q, k_cache, v_cache, q_starts, kv_lens, scale=None, return_lse=False):
+    """Causal attention of a block of ``Sq`` new tokens per sample over a KV
+    cache that already holds their K/V rows (forward only, bf16 / fp16 on the
+    GPU): chunked prefill and the follow-up turn of a session.
+
+    q: [B, Sq, H, D] (a strided view such as the packed-QKV ``select`` works);
+    caches: [B, maxlen, H, D]; q_starts, kv_lens: int [B].  Query row ``i`` of
+    sample ``b`` sits at position ``p = q_starts[b] + i`` and sees key ``j``
+    iff ``j <= p`` and ``j < min(kv_lens[b], maxlen)``.  Rows at or past
+    ``kv_lens[b]`` (the padding rows of a ragged batch) see every key below
+    it: finite, defined, and ignored by the caller.  A row that sees no key
+    (``kv_lens[b] == 0``) gives O = 0 and lse = +inf.  ``q_starts >= 0`` is
+    trusted.  Both arrays are read on the device, so the call replays from a
+    HIP graph when they are int32 already.
+
+    Head dims that are multiples of 8 up to 128 run ``fa_fwd_qoff_kernel`` on
+    GPU tensors; anything else (CPU, other head dims) the fp32 formula, rounded
+    once at the store.  Returns O [B, Sq, H, D], with ``return_lse`` also the
+    fp32 lse [B, H, Sq]."""
+    if any(t.requires_grad for t in (q, k_cache, v_cache)):
+        raise ValueError("prefill attention is forward only: an input requires grad")
+    if q.dim() != 4 or k_cache.dim() != 4 or k_cache.shape != v_cache.shape \
+            or k_cache.shape[0] != q.shape[0] or k_cache.shape[2:] != q.shape[2:]:
+        raise ValueError("prefill attention: q [B, Sq, H, D], caches [B, maxlen, H, D]")
+    B, Sq, H, D = q.shape
+    if q_starts.numel() != B or kv_lens.numel() != B:
+        raise ValueError("prefill attention: q_starts and kv_lens must be [B]")
+    scale = _default_scale(scale, D)
+    if not q.is_cuda or not _native_dim(D):
+        out, lse = _prefill_attention_formula(q, k_cache, v_cache, q_starts, kv_lens, scale)
+        return (out, lse) if return_lse else out
+    dt = _lib.dt_code(q.dtype)
+    if k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
+        raise TypeError("prefill attention: q / cache dtypes differ")
+    if q.stride(-1) != 1 or k_cache.stride() != v_cache.stride() or k_cache.stride(-1) != 1:
+        raise ValueError("prefill attention: caches must share a layout with contiguous head dim")
+    out = torch.empty(B, Sq, H, D, device=q.device, dtype=q.dtype)
+    lse = torch.empty(B * H * Sq, device=q.device, dtype=torch.float32)
+    qs = q_starts.to(device=q.device, dtype=torch.int32).contiguous()
+    kl = kv_lens.to(device=q.device, dtype=torch.int32).contiguous()
+    rc = _lib.kernels().flash_fwd_qoff(
+        dt, q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(), lse.data_ptr(),
+        _strides(q), _strides(k_cache), _strides(v_cache), _strides(out), qs.data_ptr(),
+        kl.data_ptr(), B, H, Sq, k_cache.shape[1], D, float(scale), _lib.stream())
+    if rc != 0:
+        raise RuntimeError("flash_fwd_qoff failed (%d)" % rc)
+    _lib.maybe_sync()
+    return (out, lse.view(B, H, Sq)) if return_lse else out

@@ -27,10 +27,16 @@ def main():
     ap.add_argument("--d", type=int, default=128)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16"])
+    ap.add_argument("--q-offset", type=int, nargs="*", default=None, metavar="CHUNK",
+                    help="time ops.prefill_attention instead: S keys as chunks of CHUNK queries "
+                         "over the cache (default: S in one call, and S / 4), against the plain "
+                         "causal forward of S")
     args = ap.parse_args()
     from fleetx_amd import ops
     B, S, H, D = args.b, args.s, args.h, args.d
     dt = torch.bfloat16 if args.dtype == "bf16" else torch.float16
+    if args.q_offset is not None:
+        return q_offset(ops, B, S, H, D, dt, args)
     qkv = torch.randn(B, S, H, 3, D, device="cuda", dtype=dt, requires_grad=True)
     g = torch.randn(B, S, H, D, device="cuda", dtype=dt)
     for causal in (True, False):
@@ -64,6 +70,47 @@ def main():
                               "fwd_ms": round(tf, 4), "bwd_ms": round(tb, 4),
                               "fwd_tflops": round(flops / tf / 1e9, 1),
                               "bwd_tflops": round(2.5 * flops / tb / 1e9, 1)}), flush=True)
+
+
+def q_offset(ops, B, S, H, D, dt, args):
+    """The query-offset forward at equal work: the S x S causal triangle as
+    S / CHUNK calls of CHUNK queries at offsets 0, CHUNK, ... over one cache,
+    against one call of ``flash_attention``.  One JSON line per variant; the
+    useful FLOPs are the triangle's in every line."""
+    qkv = torch.randn(B, S, H, 3, D, device="cuda", dtype=dt)
+    q, k, v = qkv.select(3, 0), qkv.select(3, 1), qkv.select(3, 2)
+    flops = 2.0 * B * H * S * S * D
+
+    def timed(fn):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / args.iters
+
+    def line(name, chunk, ms):
+        print(json.dumps({"B": B, "S": S, "H": H, "D": D, "dtype": args.dtype, "kernel": name,
+                          "chunk": chunk, "calls": S // chunk, "workgroups_per_call":
+                          B * H * ((-(-chunk // 128) + 1) // 2), "fwd_ms": round(ms, 4),
+                          "fwd_tflops": round(flops / ms / 1e9, 1)}), flush=True)
+
+    line("fa_fwd_kernel", S, timed(lambda: ops.flash_attention(q, k, v, causal=True)))
+    for chunk in (args.q_offset or [S, max(64, S // 4)]):
+        if S % chunk:
+            raise SystemExit("--q-offset: S must be a multiple of every chunk")
+        starts = [torch.full((B,), c * chunk, dtype=torch.int32, device="cuda")
+                  for c in range(S // chunk)]
+        lens = [s + chunk for s in starts]
+
+        def run():
+            for c, (s, n) in enumerate(zip(starts, lens)):
+                ops.prefill_attention(q[:, c * chunk:(c + 1) * chunk], k, v, s, n)
+        line("fa_fwd_qoff_kernel", chunk, timed(run))
 
 
 if __name__ == "__main__":

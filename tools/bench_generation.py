@@ -55,15 +55,26 @@ def main():
     ap.add_argument("--spec-device-loop", action="store_true",
                     help="also run every speculative series with Generation.spec_device_loop")
     ap.add_argument("--repeat", type=int, default=1)
+    ap.add_argument("--prefill-chunk", type=int, default=0,
+                    help="Generation.prefill_chunk for every series; each line then also "
+                         "reports the prefill's ms and peak memory")
+    ap.add_argument("--session-turns", type=int, default=0,
+                    help="instead of the series: a session of --prompt tokens, then this many "
+                         "turns of --turn-tokens new tokens, each against prefilling the whole "
+                         "transcript again without a session")
+    ap.add_argument("--turn-tokens", type=int, default=64)
+    ap.add_argument("--max-pos", type=int, default=1024, help="max_position_embeddings")
     args = ap.parse_args()
     from fleetx_amd.models.language_model.gpt.model import GPTConfig, GPTForPretraining
     from fleetx_amd.models.language_model.gpt.generation import GPTForGeneration
     h, L, a = MODELS[args.model]
     cfg = GPTConfig(vocab_size=50304, hidden_size=h, num_layers=L, num_attention_heads=a,
-                    max_position_embeddings=1024, hidden_dropout_prob=0.0,
+                    max_position_embeddings=args.max_pos, hidden_dropout_prob=0.0,
                     attention_probs_dropout_prob=0.0, dtype=torch.bfloat16)
     model = GPTForPretraining(cfg).cuda().eval()
     nbytes = sum(p.numel() * p.element_size() for p in model.parameters())
+    if args.session_turns:
+        return session_turns(model, args)
     for B in args.batch:
         prompt = torch.randint(0, 50304, (B, args.prompt), device="cuda")
         series = [(f, None, False, 0, False)
@@ -78,16 +89,20 @@ def main():
         for fused, wq, dloop, spec, sdl in series * args.repeat:
             conf = {"max_dec_len": args.tokens, "fused_decode": fused,
                     "decode_strategy": args.strategy, "num_beams": args.num_beams,
-                    "weight_quant": wq, "device_loop": dloop}
+                    "weight_quant": wq, "device_loop": dloop,
+                    "prefill_chunk": args.prefill_chunk}
             if spec:
                 conf.update(spec_draft=args.spec_draft, spec_tokens=spec, spec_device_loop=sdl)
             gen = GPTForGeneration(model, conf)
             gen.generate(prompt, max_length=8)
             torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
             t0 = time.perf_counter()
             gen.generate(prompt, max_length=1)
             torch.cuda.synchronize()
             t_pre = time.perf_counter() - t0
+            peak = torch.cuda.max_memory_allocated() - base
             t0 = time.perf_counter()
             ids, _ = gen.generate(prompt)
             torch.cuda.synchronize()
@@ -103,6 +118,9 @@ def main():
                     "ms_per_token": round(ms, 3),
                     "tokens_per_s": round(B * 1e3 / ms, 1),
                     "weight_TB_s": round(nbytes / (ms * 1e-3) / 1e12, 2)}
+            # the max_length=1 call: prefill, one selection, one decode step
+            line.update(prefill_chunk=args.prefill_chunk, prefill_ms=round(1e3 * t_pre, 3),
+                        prefill_peak_MiB=round(peak / 2 ** 20, 1))
             st = gen.last_spec_stats
             if spec and st:
                 # ms_per_token is per emitted token; the weight rate of a 16-bit
@@ -114,6 +132,47 @@ def main():
                             acceptance=round(st["accepted"] / max(1, st["drafted"]), 3),
                             ms_per_round=round(1e3 * (t - t_pre) / max(1, st["rounds"]), 3))
             print(json.dumps(line), flush=True)
+
+
+def session_turns(model, args):
+    """One JSON line per turn: ms of a turn of ``--turn-tokens`` new tokens on
+    the session (prefill of pending + new tokens at the session's offset, one
+    selection, one decode step) against the same call on the whole transcript
+    without a session; both timed twice, the second one reported."""
+    from fleetx_amd.models.language_model.gpt.generation import GPTForGeneration
+    conf = {"max_dec_len": args.tokens, "decode_strategy": args.strategy,
+            "prefill_chunk": args.prefill_chunk, "eos_token_id": None}
+    gen = GPTForGeneration(model, conf)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return out, 1e3 * (time.perf_counter() - t0)
+
+    for B in args.batch:
+        s = gen.new_session(B)
+        transcript = torch.randint(0, 50304, (B, args.prompt), device="cuda")
+        gen.generate(transcript, max_length=1, session=s)
+        for turn in range(args.session_turns):
+            new = torch.randint(0, 50304, (B, args.turn_tokens), device="cuda")
+            state = (s.lens.clone(), s.pending.clone(), list(s._lens), list(s._pending))
+            for rep in range(2):  # the first pass warms the shapes up; state restored between
+                s.lens.copy_(state[0])
+                s.pending.copy_(state[1])
+                s._lens, s._pending = list(state[2]), list(state[3])
+                (ids, _), ms_turn = timed(lambda: gen.generate(new, max_length=1, session=s))
+            pend = state[1][:, None]
+            transcript = torch.cat([transcript, pend, new], 1)
+            for rep in range(2):
+                _, ms_full = timed(lambda: gen.generate(transcript, max_length=1))
+            print(json.dumps({"model": args.model, "batch": B, "turn": turn + 1,
+                              "context": int(state[0][0]), "turn_tokens": args.turn_tokens,
+                              "prefill_chunk": args.prefill_chunk,
+                              "session_turn_ms": round(ms_turn, 3),
+                              "full_prefill_ms": round(ms_full, 3),
+                              "speedup": round(ms_full / ms_turn, 2)}), flush=True)
 
 
 if __name__ == "__main__":
