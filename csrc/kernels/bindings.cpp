@@ -231,27 +231,37 @@ PYBIND11_MODULE(_kernels, m) {
                      float top_p, ptr u, int n_steps, int eos, int pad, int min_len, float pen,
                      float inv_pen, int bos, int feos, int feos_step, ptr seen, int words,
                      ptr step, ptr unfinished, ptr finish_len, ptr scores, ptr out, ptr nxt,
-                     ptr cur, ptr lens, ptr st) {
+                     ptr cur, ptr lens, ptr st, ptr seed) {
     return fx_select(F(logits), ld, B, V, sampling, inv_temp, top_k, top_p, F(u), n_steps, eos,
                      pad, min_len, pen, inv_pen, bos, feos, feos_step,
                      reinterpret_cast<unsigned int*>(seen), words, reinterpret_cast<int*>(step),
                      reinterpret_cast<int*>(unfinished), reinterpret_cast<int*>(finish_len),
                      F(scores), reinterpret_cast<int64_t*>(out), reinterpret_cast<int64_t*>(nxt),
                      reinterpret_cast<int64_t*>(cur), reinterpret_cast<const int64_t*>(lens),
-                     S(st));
+                     S(st), reinterpret_cast<const int64_t*>(seed));
+  });
+  m.def("coupled_sample", [](ptr logits, long ld, int R, int V, float inv_temp, int top_k,
+                             float top_p, ptr steps, ptr rows, ptr seed, ptr ids, ptr lse,
+                             ptr st) {
+    return fx_coupled_sample(F(logits), ld, R, V, inv_temp, top_k, top_p,
+                             reinterpret_cast<const int*>(steps),
+                             reinterpret_cast<const int*>(rows),
+                             reinterpret_cast<const int64_t*>(seed),
+                             reinterpret_cast<int64_t*>(ids), F(lse), S(st));
   });
   m.def("spec_verify", [](ptr logits, long ld, int B, int W, int V, int n_steps, int eos, int pad,
                           int min_len, float pen, float inv_pen, int feos, int feos_step, ptr seen,
                           int words, ptr step, ptr unfinished, ptr finish_len, ptr scores, ptr out,
                           ptr nxt, ptr cur, ptr tok, ptr pos, ptr wlens, ptr picks, ptr logp,
-                          ptr rounds, ptr accepted, ptr any_active, ptr st) {
+                          ptr rounds, ptr accepted, ptr any_active, ptr st, int coupled,
+                          float inv_temp, int top_k, float top_p, ptr seed) {
     auto I = [](ptr p) { return reinterpret_cast<int*>(p); };
     auto L = [](ptr p) { return reinterpret_cast<int64_t*>(p); };
     return fx_spec_verify(F(logits), ld, B, W, V, n_steps, eos, pad, min_len, pen, inv_pen, feos,
                           feos_step, reinterpret_cast<unsigned int*>(seen), words, I(step),
                           I(unfinished), I(finish_len), F(scores), L(out), L(nxt), L(cur), L(tok),
                           L(pos), I(wlens), I(picks), F(logp), I(rounds), I(accepted),
-                          I(any_active), S(st));
+                          I(any_active), S(st), coupled, inv_temp, top_k, top_p, L(seed));
   });
   m.def("decode_attn", [](int dt, ptr q, ptr kc, ptr vc, ptr out, ptr lens, int B, int H, int D,
                           int maxlen, int nsplit, ptr ws, long sqb, long sqh, long skb, long sks,

@@ -84,13 +84,18 @@ int fx_select(const float* logits, long ld_row, int B, int V, int sampling, floa
               int top_k, float top_p, const float* u, int n_steps, int eos, int pad, int min_len,
               float pen, float inv_pen, int bos, int feos, int feos_step, unsigned int* seen,
               int words, int* step, int* unfinished, int* finish_len, float* scores,
-              int64_t* out, int64_t* nxt, int64_t* cur, const int64_t* lens, hipStream_t);
+              int64_t* out, int64_t* nxt, int64_t* cur, const int64_t* lens, hipStream_t,
+              const int64_t* seed);
+int fx_coupled_sample(const float* logits, long ld_row, int R, int V, float inv_temp, int top_k,
+                      float top_p, const int* steps, const int* rows, const int64_t* seed,
+                      int64_t* out_ids, float* out_lse, hipStream_t);
 int fx_spec_verify(const float* logits, long ld_row, int B, int W, int V, int n_steps, int eos,
                    int pad, int min_len, float pen, float inv_pen, int feos, int feos_step,
                    unsigned int* seen, int words, int* step, int* unfinished, int* finish_len,
                    float* scores, int64_t* out, int64_t* nxt, int64_t* cur, int64_t* tok,
                    int64_t* pos, int* wlens, int* picks, float* logp, int* rounds, int* accepted,
-                   int* any_active, hipStream_t);
+                   int* any_active, hipStream_t, int coupled, float inv_temp, int top_k,
+                   float top_p, const int64_t* seed);
 int fx_decode_attn(int, const void*, const void*, const void*, void*, const int*, int, int, int,
                    int, int, float*, long, long, long, long, long, long, float, hipStream_t);
 int fx_beam_decode_attn(int, const void*, const void*, const void*, const int*, const void*,

@@ -20,6 +20,13 @@
 //      contiguous chunks, block exclusive scan of chunk masses, the owning
 //      thread walks its chunk.
 //
+// The coupled sampler (coupled_row) replaces phase 4 by a Gumbel race over the
+// same kept set: argmax_i (x_i / T + g_i) with noise g that depends only on
+// (seed, token index t, row b, vocabulary index i).  Whoever picks token t of
+// row b -- a draft step, a window slot, the plain loop -- draws with the same
+// noise, so speculative decoding under sampling accepts a draft iff it equals
+// the target's pick, as the greedy loop does.
+//
 // Every pass re-reads the row from global memory (a 50k-entry fp32 row is
 // 200 KB: L2-resident, larger than LDS); decode batches are small, so the
 // kernel is latency- not bandwidth-bound and one launch replaces ~15.
@@ -250,6 +257,61 @@ __device__ __forceinline__ int draw_token(const P& prob, int V, unsigned int thr
   return s.pick < 0 ? 0 : s.pick;
 }
 
+// ---- the coupled pick: shared Gumbel noise instead of a uniform
+// The key of token index `t` in row `b`; must match parallel/rng.py:coupled_key.
+__device__ __forceinline__ uint64_t coupled_key(uint64_t seed, int t, int b) {
+  const uint64_t tb = ((uint64_t)(uint32_t)t << 32) | (uint32_t)b;
+  return fx_mix64(fx_mix64(seed + 0x9E3779B97F4A7C15ull) ^ tb);
+}
+// g_i = -log(-log(U)), U = ((h >> 9) + 0.5) * 2^-23 in (0, 1): 23 bits are exact
+// in fp32 (24 would round the top value to 1 and g to +inf).  The accurate
+// logf: E = -log(U) reaches 6e-8, where an absolute error is a large relative one.
+__device__ __forceinline__ float coupled_gumbel(uint32_t klo, uint32_t khi, int i) {
+  const uint32_t h = lowbias32(lowbias32((uint32_t)i ^ klo) ^ khi);
+  const float u = ((float)(h >> 9) + 0.5f) * 1.1920928955078125e-07f;
+  return -logf(-logf(u));
+}
+
+// 4'. Gumbel race over the kept set: the index of the largest
+//     key_i = fma(load(i), inv_temp, g_i), the lowest index among equal keys;
+//     every thread returns the pick (0 when nothing survives)
+template <typename L, typename P>
+__device__ __forceinline__ int race_token(const L& load, const P& prob, int V, unsigned int thr,
+                                          float inv_temp, uint64_t key, Shared& s) {
+  const int tid = threadIdx.x;
+  const uint32_t klo = (uint32_t)key, khi = (uint32_t)(key >> 32);
+  float best = -INFINITY;
+  int first = V;
+  for (int i = tid; i < V; i += ST) {
+    if (thr != 0u && __float_as_uint(prob(i)) < thr) continue;
+    const float k = __fmaf_rn(load(i), inv_temp, coupled_gumbel(klo, khi, i));
+    if (k > best) {  // ascending i: the lowest index of the thread's maximum
+      best = k;
+      first = i;
+    }
+  }
+  const float m = block_max(best, s);
+  if (tid == 0) s.pick = V;
+  __syncthreads();
+  if (first < V && best == m) atomicMin(&s.pick, first);
+  __syncthreads();
+  return s.pick < V ? s.pick : 0;
+}
+
+// phases 1-3 and the race on load(i) for token index `t` of row `b`; returns
+// the pick, `lse` is the logsumexp of load(i).  The kept set is sample_row's.
+template <typename L>
+__device__ __forceinline__ int coupled_row(const L& load, int V, float inv_temp, int top_k,
+                                           float top_p, uint64_t seed, int t, int b, Shared& s,
+                                           float& lse) {
+  float m, inv_se;
+  softmax_stats(load, V, inv_temp, s, m, inv_se, lse);
+  auto prob = [&](int i) { return __expf(load(i) * inv_temp - m) * inv_se; };
+  const unsigned int kth = topk_threshold(prob, V, top_k, s);
+  const unsigned int pth = topp_threshold(prob, V, top_p, kth, s);
+  return race_token(load, prob, V, kth > pth ? kth : pth, inv_temp, coupled_key(seed, t, b), s);
+}
+
 // phases 1-4 on load(i); returns the pick, `lse` is the logsumexp of load(i)
 template <typename L>
 __device__ __forceinline__ int sample_row(const L& load, int V, float inv_temp, int top_k,
@@ -283,6 +345,27 @@ __global__ __launch_bounds__(ST) void sample_kernel(const T* __restrict__ logits
   }
 }
 
+// The coupled pick of R rows of raw logits: row r chooses token index steps[r]
+// of noise row rows[r] (r itself without `rows`).  Steps, rows and the seed are
+// read from device memory, so a captured launch follows them under replay.
+__global__ __launch_bounds__(ST) void coupled_sample_kernel(
+    const float* __restrict__ logits, long ld_row, int V, float inv_temp, int top_k, float top_p,
+    const int* __restrict__ steps, const int* __restrict__ rows,
+    const int64_t* __restrict__ seed, int64_t* __restrict__ out_ids,
+    float* __restrict__ out_lse) {
+  __shared__ Shared s;
+  const int row = blockIdx.x;
+  const float* lg = logits + row * ld_row;
+  auto load = [&](int i) { return lg[i]; };
+  float lse;
+  const int pick = coupled_row(load, V, inv_temp, top_k, top_p, (uint64_t)seed[0], steps[row],
+                               rows ? rows[row] : row, s, lse);
+  if (threadIdx.x == 0) {
+    if (out_lse) out_lse[row] = lse;
+    out_ids[row] = pick;
+  }
+}
+
 // ---------------------------------------------------------------- selection
 // One decode step's token selection, state in device memory (K18, K19): the
 // logits processors applied on the load, the pick (greedy or phases 1-4
@@ -292,7 +375,7 @@ struct SelectArgs {
   const float* logits;      // [B, V] fp32, read-only
   long ld_row;
   int V, B;
-  int sampling;             // 0: greedy, 1: top-k / top-p sampling
+  int sampling;             // 0: greedy, 1: top-k / top-p sampling, 2: the coupled pick
   float inv_temp;
   int top_k;
   float top_p;
@@ -314,6 +397,7 @@ struct SelectArgs {
   int64_t* nxt;             // [B] the decode graph's static inputs
   int64_t* cur;
   const int64_t* lens;      // [B]
+  const int64_t* seed;      // [1] (sampling == 2)
 };
 
 // the processed logit x'(i), in the order of GPTForGeneration._processors()
@@ -407,7 +491,10 @@ __global__ __launch_bounds__(ST) void select_kernel(SelectArgs a) {
   int pick = 0;
   float lse = 0.f;
   if (unf) {  // a finished row emits pad: nothing to pick
-    if (a.sampling) {
+    if (a.sampling == 2) {
+      pick = coupled_row(load, a.V, a.inv_temp, a.top_k, a.top_p, (uint64_t)a.seed[0], step, row,
+                         s, lse);
+    } else if (a.sampling) {
       pick = sample_row(load, a.V, a.inv_temp, a.top_k, a.top_p, a.u[(long)step * a.B + row],
                         nullptr, s, lse);
     } else {
@@ -430,9 +517,9 @@ __global__ __launch_bounds__(ST) void select_kernel(SelectArgs a) {
 }
 
 // ------------------------------------------------------ speculative verify
-// One round of speculative greedy decoding after the window step, state in
-// device memory: spec_pick_kernel takes the target's greedy pick of every
-// window slot, spec_accept_kernel does the bookkeeping the host loop does
+// One round of speculative decoding after the window step, state in device
+// memory: spec_pick_kernel takes the target's pick of every window slot (the
+// greedy one, or the coupled one under sampling), spec_accept_kernel does the bookkeeping the host loop does
 // between two window steps.  Two launches on one stream, so the second sees
 // all picks without a grid-wide sync; a row's state belongs to one thread.
 struct SpecArgs {
@@ -462,13 +549,18 @@ struct SpecArgs {
   int* rounds;              // [B]
   int* accepted;            // [B]
   int* any_active;          // [1]
+  float inv_temp;           // the coupled pick's sampler settings and seed [1]
+  int top_k;
+  float top_p;
+  const int64_t* seed;
 };
 
 // Workgroup (b, j): the processed logits of slot j, which chooses token
 // step[b] + j from the history plus the drafts d_1 .. d_j, and their greedy
-// pick.  A row that no longer emits is skipped.  Slots at or past n_steps are
+// pick (COUPLED: their coupled pick with token index step[b] + j, row b).  A row that no longer emits is skipped.  Slots at or past n_steps are
 // picked as well (they are never emitted): the acceptance count covers them,
 // as the host loop's does.
+template <bool COUPLED>
 __global__ __launch_bounds__(ST) void spec_pick_kernel(SpecArgs a) {
   __shared__ Shared s;
   const int b = blockIdx.x / a.W, j = blockIdx.x % a.W;
@@ -492,7 +584,12 @@ __global__ __launch_bounds__(ST) void spec_pick_kernel(SpecArgs a) {
     }
   }
   float lse;
-  const int pick = greedy_row(load, a.V, s, lse);
+  int pick;
+  if constexpr (COUPLED)
+    pick = coupled_row(load, a.V, a.inv_temp, a.top_k, a.top_p, (uint64_t)a.seed[0], sj, b, s,
+                       lse);
+  else
+    pick = greedy_row(load, a.V, s, lse);
   if (threadIdx.x == 0) {
     a.picks[blockIdx.x] = pick;
     a.logp[blockIdx.x] = load(pick) - lse;
@@ -528,7 +625,7 @@ __global__ __launch_bounds__(64) void spec_accept_kernel(SpecArgs a) {
       unsigned int* seen = a.seen + (long)b * a.words;
       float sc = a.scores[b];
       for (int j = 0; j < m; ++j) {
-        const int t = picks[j];  // in [0, V): greedy_row's result
+        const int t = picks[j];  // in [0, V): the result of greedy_row / coupled_row
         a.out[(long)b * a.n_steps + step + j] = t;
         seen[t >> 5] |= 1u << (t & 31);
         sc += a.logp[b * W + j];
@@ -569,14 +666,27 @@ extern "C" int fx_sample(int dtype, const void* logits, long ld_row, int B, int 
   return 0;
 }
 
+extern "C" int fx_coupled_sample(const float* logits, long ld_row, int R, int V, float inv_temp,
+                                 int top_k, float top_p, const int* steps, const int* rows,
+                                 const int64_t* seed, int64_t* out_ids, float* out_lse,
+                                 hipStream_t st) {
+  if (R <= 0 || V <= 0) return 0;
+  if (!logits || !steps || !seed || !out_ids) return -1;
+  coupled_sample_kernel<<<R, ST, 0, st>>>(logits, ld_row, V, inv_temp, top_k, top_p, steps, rows,
+                                          seed, out_ids, out_lse);
+  return 0;
+}
+
 extern "C" int fx_select(const float* logits, long ld_row, int B, int V, int sampling,
                          float inv_temp, int top_k, float top_p, const float* u, int n_steps,
                          int eos, int pad, int min_len, float pen, float inv_pen, int bos,
                          int feos, int feos_step, unsigned int* seen, int words, int* step,
                          int* unfinished, int* finish_len, float* scores, int64_t* out,
-                         int64_t* nxt, int64_t* cur, const int64_t* lens, hipStream_t st) {
+                         int64_t* nxt, int64_t* cur, const int64_t* lens, hipStream_t st,
+                         const int64_t* seed) {
   if (B <= 0 || V <= 0 || n_steps <= 0) return 0;
-  if (words < (V + 31) / 32 || (sampling && !u)) return -1;
+  if (sampling < 0 || sampling > 2) return -1;
+  if (words < (V + 31) / 32 || (sampling == 1 && !u) || (sampling == 2 && !seed)) return -1;
   if (pad < 0 || pad >= V || eos >= V || bos >= V || feos >= V) return -2;
   SelectArgs a;
   a.logits = logits, a.ld_row = ld_row, a.V = V, a.B = B;
@@ -587,7 +697,7 @@ extern "C" int fx_select(const float* logits, long ld_row, int B, int V, int sam
   a.bos = bos, a.feos = feos, a.feos_step = feos_step;
   a.seen = seen, a.words = words, a.step = step, a.unfinished = unfinished;
   a.finish_len = finish_len, a.scores = scores, a.out = out, a.nxt = nxt, a.cur = cur;
-  a.lens = lens;
+  a.lens = lens, a.seed = seed;
   select_kernel<<<B, ST, 0, st>>>(a);
   return 0;
 }
@@ -598,9 +708,10 @@ extern "C" int fx_spec_verify(const float* logits, long ld_row, int B, int W, in
                               int* unfinished, int* finish_len, float* scores, int64_t* out,
                               int64_t* nxt, int64_t* cur, int64_t* tok, int64_t* pos, int* wlens,
                               int* picks, float* logp, int* rounds, int* accepted,
-                              int* any_active, hipStream_t st) {
+                              int* any_active, hipStream_t st, int coupled, float inv_temp,
+                              int top_k, float top_p, const int64_t* seed) {
   if (B <= 0 || V <= 0 || n_steps <= 0) return 0;
-  if (words < (V + 31) / 32) return -1;
+  if (words < (V + 31) / 32 || (coupled && !seed)) return -1;
   if (pad < 0 || pad >= V || eos >= V || feos >= V) return -2;
   if (W < 1 || W > MAXW || B > 64) return -3;
   SpecArgs a;
@@ -612,7 +723,11 @@ extern "C" int fx_spec_verify(const float* logits, long ld_row, int B, int W, in
   a.finish_len = finish_len, a.scores = scores, a.out = out, a.nxt = nxt, a.cur = cur;
   a.tok = tok, a.pos = pos, a.wlens = wlens, a.picks = picks, a.logp = logp;
   a.rounds = rounds, a.accepted = accepted, a.any_active = any_active;
-  spec_pick_kernel<<<B * W, ST, 0, st>>>(a);
+  a.inv_temp = inv_temp, a.top_k = top_k, a.top_p = top_p, a.seed = seed;
+  if (coupled)
+    spec_pick_kernel<true><<<B * W, ST, 0, st>>>(a);
+  else
+    spec_pick_kernel<false><<<B * W, ST, 0, st>>>(a);
   spec_accept_kernel<<<1, 64, 0, st>>>(a);
   return 0;
 }

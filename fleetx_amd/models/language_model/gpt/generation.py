@@ -32,7 +32,12 @@ MI355X design (K18/K19):
   ids and scores, whatever the drafter proposes.  With ``spec_device_loop``
   the per-slot processors, picks, acceptance and EOS bookkeeping run in two
   kernels behind the window step (``ops.spec_verify``) and a whole round is
-  one HIP graph replay.
+  one HIP graph replay;
+* ``sampler: coupled`` draws every sampled token as a Gumbel race with noise
+  that depends only on (seed, token index, row, vocabulary index)
+  (``ops.coupled_sample``), so draft and target draw with the same noise and
+  the speculative loops above run under ``decode_strategy: sampling`` as they
+  do under greedy search: a draft is accepted iff it equals the target's pick.
 """
 import os
 import warnings
@@ -520,14 +525,27 @@ class _GraphedDraftStep(_GraphedDecodeStep):
     """One draft token as one graph: a plain decode step on the draft copies
     (LM head included), the argmax, and the advance of the step's own inputs
     ``nxt`` / ``cur``, so ``k`` replays draft ``k`` tokens with no host work
-    between them."""
+    between them.  After ``couple(seed)`` the pick is the coupled one
+    (``ops.coupled_sample`` on the raw draft logits) with the token index in
+    the static tensor ``steps``, which advances with ``cur``."""
+
+    steps = seed = None
+
+    def couple(self, seed):
+        self.seed = seed.clone()
+        self.steps = torch.zeros(self.nxt.shape[0], dtype=torch.int32, device=self.nxt.device)
 
     def _run(self):
         gen, cur = self.gen, self.cur
         ids = cur.clamp(max=gen.gpt.cfg.max_position_embeddings - 1)
         logits = gen._step(self.nxt, ids, self.cache, cur, (cur + 1).to(torch.int32),
                            copies=gen._wd)
-        self.nxt.copy_(torch.argmax(logits, -1))
+        if self.steps is None:
+            self.nxt.copy_(torch.argmax(logits, -1))
+        else:
+            self.nxt.copy_(ops.coupled_sample(logits, gen.temperature, gen.top_k, gen.top_p,
+                                              self.seed, self.steps)[0])
+            self.steps.add_(1)
         cur.add_(1)
         return logits
 
@@ -551,6 +569,8 @@ class _GraphedSpecRound(_GraphedDecodeStep):
         self.rows = torch.arange(B, dtype=torch.int32,
                                  device=state.tok.device).repeat_interleave(W)
         self.draft = _GraphedDraftStep(gen, cache, B) if draft else None
+        if draft and state.coupled:
+            self.draft.couple(state.seed)
 
     def __call__(self):
         if self.gen.use_hip_graph and self.nxt.is_cuda:
@@ -563,6 +583,8 @@ class _GraphedSpecRound(_GraphedDecodeStep):
         if d is not None:
             d.nxt.copy_(st.nxt)
             d.cur.copy_(st.cur)
+            if d.steps is not None:  # draft i guesses token step + i - 1
+                d.steps.copy_(st.step)
             tok = st.tok.view(-1, st.window)
             for i in range(st.window - 1):
                 d._run()
@@ -570,6 +592,29 @@ class _GraphedSpecRound(_GraphedDecodeStep):
         logits = self.gen._window_step(st.tok, st.pos, self.rows, st.wlens, self.cache)
         ops.spec_verify(logits, st)
         return logits
+
+
+class _CoupledPick:
+    """The ``pick`` of ``propose_coupled``: ``pick(logits [B, V], i)`` is the
+    coupled pick for draft ``i`` in ``1..k``, a guess at token ``step + i - 1``.
+    ``seed`` (int64 [1]) and ``step`` (the tokens emitted so far, [B]) are the
+    run's device tensors."""
+
+    def __init__(self, gen, seed, step):
+        self.gen, self.seed, self.step = gen, seed, step
+
+    def __call__(self, logits, i):
+        g = self.gen
+        return ops.coupled_sample(logits, g.temperature, g.top_k, g.top_p, self.seed,
+                                  self.step.to(logits.device) + (i - 1))[0]
+
+
+def _propose(drafter, last, cur, cache, k, pick):
+    """The drafter's ``k`` tokens: ``propose_coupled`` under the coupled sampler
+    if it defines one, else ``propose``."""
+    if pick is not None and hasattr(drafter, "propose_coupled"):
+        return drafter.propose_coupled(last, cur, cache, k, pick)
+    return drafter.propose(last, cur, cache, k)
 
 
 class _QuantDrafter:
@@ -583,11 +628,19 @@ class _QuantDrafter:
         self.step = None
 
     def propose(self, last, cur, cache, k):
+        return self.propose_coupled(last, cur, cache, k, None)
+
+    def propose_coupled(self, last, cur, cache, k, pick):
         if self.step is None or self.step.cache is not cache:
             self.step = _GraphedDraftStep(self.gen, cache, last.shape[0])
+            if pick is not None:
+                self.step.couple(pick.seed)
         st = self.step
         st.nxt.copy_(last)
         st.cur.copy_(cur)
+        if pick is not None:
+            st.seed.copy_(pick.seed)
+            st.steps.copy_(pick.step)
         out = torch.empty(last.shape[0], k, dtype=torch.long, device=last.device)
         for i in range(k):
             if self.gen.use_hip_graph:
@@ -610,6 +663,12 @@ class GPTForGeneration(torch.nn.Module):
         self.max_length = c.get("max_dec_len", 20)
         self.min_length = c.get("min_dec_len", 0)
         self.decode_strategy = c.get("decode_strategy", "sampling")
+        # the sampling draw: inverse CDF with a uniform per row, or the coupled pick (a
+        # Gumbel race with noise shared by index), under which speculation may sample
+        self.sampler = c.get("sampler", "inverse_cdf")
+        if self.sampler not in ("inverse_cdf", "coupled"):
+            raise ValueError("sampler must be 'inverse_cdf' or 'coupled' (got %r)"
+                             % (self.sampler,))
         self.temperature = c.get("temperature", 1.0)
         self.top_k = c.get("top_k", 0)
         self.top_p = c.get("top_p", 1.0)
@@ -683,18 +742,36 @@ class GPTForGeneration(torch.nn.Module):
     def _spec_check(self):
         if not 1 <= self.spec_tokens <= 7:
             raise ValueError("spec_tokens must be in 1..7 (got %r)" % (self.spec_tokens,))
-        if self.decode_strategy != "greedy_search" or self.device_loop \
+        if not (self.decode_strategy == "greedy_search" or self._coupled()) or self.device_loop \
                 or self.num_return_sequences > 1:
-            raise ValueError("speculative decoding supports greedy_search only, without "
-                             "device_loop and with num_return_sequences 1")
+            raise ValueError("speculative decoding supports greedy_search, or sampling with "
+                             "sampler: coupled, without device_loop and with "
+                             "num_return_sequences 1")
+
+    def _coupled(self):
+        return self.decode_strategy == "sampling" and self.sampler == "coupled"
+
+    def _coupled_seed(self, seed, dev):
+        """The seed tensor of a coupled run (None otherwise): ``generate(seed=)``,
+        or one drawn from torch's default generator."""
+        if not self._coupled():
+            return None
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        return ops.sampling.seed_tensor(seed, dev)
 
     def set_drafter(self, drafter):
-        """Install the drafter of speculative greedy decoding (any device): an
+        """Install the drafter of speculative decoding (any device): an
         object with ``propose(last, cur, cache, k) -> LongTensor [B, k]``, the
         ``k`` tokens it expects after ``last`` [B], which sits at position
         ``cur`` [B] and is not in ``cache`` yet.  It may write cache rows
         ``cur .. cur+k-1``; the verify step overwrites them.  The output is
-        the target's whatever it proposes.  ``None`` removes it."""
+        the target's whatever it proposes.  Under ``sampler: coupled`` a
+        drafter that defines ``propose_coupled(last, cur, cache, k, pick)`` is
+        asked through it: ``pick(logits [B, V], i)`` is the coupled pick for
+        draft ``i`` in ``1..k`` (the target's own noise for that token, so a
+        draft model close to the target is accepted as often as the coupling
+        allows).  ``None`` removes it."""
         if drafter is not None:
             self._spec_check()
         self._drafter = drafter
@@ -956,7 +1033,13 @@ class GPTForGeneration(torch.nn.Module):
         Seeded sampling is reproducible under ``device_loop`` but draws its
         uniforms in a different order (one ``[N, B]`` table up front; on the
         CPU an inverse-CDF draw instead of ``torch.multinomial``), so a seed
-        does not give the default loop's tokens."""
+        does not give the default loop's tokens.
+
+        With ``sampler: coupled`` token ``t`` of row ``b`` (the row of the
+        expanded batch) is the coupled pick of ``(seed, t, b)`` in every loop
+        (host loop, ``device_loop``, sessions, the speculative loops), so a
+        seed gives one text per path of logits; without ``seed`` one is drawn
+        from torch's default generator."""
         self.eval()
         if session is not None:
             return self._generate_turn(session, input_ids, lens, max_length, seed)
@@ -984,22 +1067,26 @@ class GPTForGeneration(torch.nn.Module):
         if seed is not None:
             gen = torch.Generator(device=dev)
             gen.manual_seed(seed)
+        cseed = self._coupled_seed(seed, dev)
         # ---- prefill
         logits = self._prompt_logits(input_ids, lens, cache, lens.to(torch.int32))
         eos = self.eos_token_id
         pad = self.pad_token_id if self.pad_token_id is not None else (eos if eos is not None else 0)
         if self.device_loop:
             if topo.mp_world_size() == 1:
-                return self._device_loop(input_ids, lens, logits, cache, max_new, pad, gen)
+                return self._device_loop(input_ids, lens, logits, cache, max_new, pad, gen,
+                                         cseed)
             if not self._device_loop_warned:
                 warnings.warn("device_loop is ignored under tensor parallelism")
                 self._device_loop_warned = True
         if drafter is not None and self.spec_device_loop:
-            return self._speculative_device(input_ids, lens, logits, cache, max_new, pad, drafter)
+            return self._speculative_device(input_ids, lens, logits, cache, max_new, pad, drafter,
+                                            cseed)
         if drafter is not None:
-            return self._speculative(input_ids, lens, logits, cache, max_new, pad, total, drafter)
+            return self._speculative(input_ids, lens, logits, cache, max_new, pad, total, drafter,
+                                     cseed)
         out_tokens, scores, _ = self._host_loop(logits, input_ids.clone(), lens.clone(), cache,
-                                                total, max_new, pad, gen)
+                                                total, max_new, pad, gen, seed=cseed)
         if not out_tokens:
             return torch.zeros(B, 0, dtype=torch.long, device=dev), scores
         return torch.stack(out_tokens, 1), scores
@@ -1015,6 +1102,7 @@ class GPTForGeneration(torch.nn.Module):
         if seed is not None:
             gen = torch.Generator(device=dev)
             gen.manual_seed(seed)
+        cseed = self._coupled_seed(seed, dev)
         start = list(s._lens)
         Sp = tok.shape[1]
         if not any(start) and not (self.prefill_chunk and Sp > self.prefill_chunk):
@@ -1033,7 +1121,8 @@ class GPTForGeneration(torch.nn.Module):
         pad = self.pad_token_id if self.pad_token_id is not None else (eos if eos is not None else 0)
         total = min(max(end) + max_new, s.max_len)
         out_tokens, scores, emitted = self._host_loop(logits, s.history(), cur.clone(), s.cache,
-                                                      total, max_new, pad, gen, count=True)
+                                                      total, max_new, pad, gen, count=True,
+                                                      seed=cseed)
         if not out_tokens:
             return torch.zeros(B, 0, dtype=torch.long, device=dev), scores
         out = torch.stack(out_tokens, 1)
@@ -1049,12 +1138,15 @@ class GPTForGeneration(torch.nn.Module):
         s._pending = [int(t) for t in pending.tolist()]
         return out, scores
 
-    def _host_loop(self, logits, history, cur, cache, total, max_new, pad, gen, count=False):
+    def _host_loop(self, logits, history, cur, cache, total, max_new, pad, gen, count=False,
+                   seed=None):
         """The sampling / greedy loop on the host: ``logits`` [B, V] choose the
         first token, ``history`` [B, L] feeds the processors, ``cur`` [B] is
         the position of the next token, positions stay below ``total``.
         Returns the list of [B] token tensors, the scores [B] and, with
-        ``count``, the tokens each row emitted (up to and including its EOS)."""
+        ``count``, the tokens each row emitted (up to and including its EOS).
+        With ``seed`` (``sampler: coupled``) token ``step`` of row ``b`` is the
+        coupled pick of index ``(step, b)``."""
         B = logits.shape[0]
         dev = logits.device
         eos = self.eos_token_id
@@ -1071,7 +1163,12 @@ class GPTForGeneration(torch.nn.Module):
                 if hasattr(pr, "cur_len"):
                     pr.cur_len = step
             logits = procs(history, logits)
-            if self.decode_strategy != "greedy_search" and logits.is_cuda:
+            if seed is not None:
+                nxt, lse = ops.coupled_sample(
+                    logits, self.temperature, self.top_k, self.top_p, seed,
+                    torch.full((B,), step, dtype=torch.int32, device=dev))
+                step_score = logits.gather(1, nxt[:, None]).squeeze(1).float() - lse
+            elif self.decode_strategy != "greedy_search" and logits.is_cuda:
                 # one fused HIP launch: softmax/T, top-k, top-p, draw, logsumexp
                 nxt, lse = ops.fused_sample(logits, self.temperature, self.top_k, self.top_p,
                                             generator=gen)
@@ -1161,14 +1258,15 @@ class GPTForGeneration(torch.nn.Module):
             lj[:, self.forced_eos_token_id] = torch.where(f, torch.zeros_like(col), col)
         return lj
 
-    def _speculative(self, input_ids, lens, logits, cache, max_new, pad, total, drafter):
-        """Greedy search in rounds of {draft ``spec_tokens`` tokens, verify them
+    def _speculative(self, input_ids, lens, logits, cache, max_new, pad, total, drafter,
+                     seed=None):
+        """Greedy search, or with ``seed`` coupled sampling, in rounds of {draft ``spec_tokens`` tokens, verify them
         and one more position in one window step of the target weights, keep
         the longest agreeing prefix plus the target's next token}.  ``logits``
         are the prefill's (they choose token 0).
 
-        Every emitted token is the argmax of processed target logits, so ids
-        and scores are the target's; the drafter only decides how many window
+        Every emitted token is the argmax (the coupled pick of its token index
+        and row) of processed target logits, so ids and scores are the target's; the drafter only decides how many window
         steps are run.  Past the first token every cache row is written by a
         window step of ``B * (spec_tokens + 1)`` rows, whose row results do not
         depend on the slot, so the output does not depend on the drafter
@@ -1196,8 +1294,18 @@ class GPTForGeneration(torch.nn.Module):
             if hasattr(pr, "cur_len"):
                 pr.cur_len = 0
         logits = procs(input_ids, logits)
-        last = torch.argmax(logits, -1)
-        scores = torch.log_softmax(logits, -1).gather(1, last[:, None]).squeeze(1)
+        rowid = torch.arange(B, dtype=torch.int32, device=dev)
+
+        def choose(x, steps, rows):
+            """The picks of the rows of ``x`` [R, V] and their log-probabilities."""
+            if seed is None:
+                t = torch.argmax(x, -1)
+                return t, torch.log_softmax(x, -1).gather(1, t[:, None]).squeeze(1)
+            t, lse = ops.coupled_sample(x, self.temperature, self.top_k, self.top_p, seed,
+                                        steps, rows)
+            return t, x.gather(1, t[:, None]).squeeze(1).float() - lse
+
+        last, scores = choose(logits, torch.zeros_like(rowid), rowid)
         # W slack columns: a row's window may reach past the last emitted token
         out = torch.full((B, T + W), pad, dtype=torch.long, device=dev)
         out[:, 0] = last
@@ -1215,11 +1323,14 @@ class GPTForGeneration(torch.nn.Module):
             graphed = _GraphedWindowStep(self, cache, B, W)
         rows = torch.arange(B, dtype=torch.int32, device=dev).repeat_interleave(W)
         plain_logits = all(isinstance(pr, ForcedBOSTokenLogitsProcessor) for pr in procs)
+        pick = None if seed is None else _CoupledPick(self, seed, emitted)
         while True:
             active = unfinished & (emitted < T)
             if not bool(active.any()):
                 break
-            d = drafter.propose(last, cur, cache, g).to(device=dev, dtype=torch.long)
+            if pick is not None:
+                pick.step = emitted
+            d = _propose(drafter, last, cur, cache, g, pick).to(device=dev, dtype=torch.long)
             tok = torch.cat([last[:, None], d], 1).reshape(-1)
             pos = (cur[:, None] + ar[None, :]).reshape(-1)
             before = cur.to(torch.int32)
@@ -1230,8 +1341,8 @@ class GPTForGeneration(torch.nn.Module):
             idx = emitted[:, None] + ar[None, :]
             hist.scatter_(1, S + idx[:, :g], d)
             if plain_logits:  # no processor acts past token 0: all slots at once
-                t = torch.argmax(lg, -1)
-                lp = torch.log_softmax(lg, -1).gather(2, t[:, :, None]).squeeze(2)
+                t, lp = choose(lg.reshape(B * W, -1), idx.reshape(-1), rowid.repeat_interleave(W))
+                t, lp = t.view(B, W), lp.view(B, W)
             else:
                 t = torch.empty(B, W, dtype=torch.long, device=dev)
                 lp = torch.empty(B, W, device=dev)
@@ -1239,8 +1350,7 @@ class GPTForGeneration(torch.nn.Module):
                     step = emitted + j
                     lj = self._spec_process(lg[:, j], hist, cols < (S + step)[:, None], step,
                                             max_new)
-                    t[:, j] = torch.argmax(lj, -1)
-                    lp[:, j] = torch.log_softmax(lj, -1).gather(1, t[:, j:j + 1]).squeeze(1)
+                    t[:, j], lp[:, j] = choose(lj, step, rowid)
             n = (d == t[:, :g]).long().cumprod(1).sum(1)      # accepted draft tokens
             m = torch.minimum(n + 1, T - emitted)
             emit = (ar[None, :] < m[:, None]) & active[:, None]
@@ -1266,7 +1376,8 @@ class GPTForGeneration(torch.nn.Module):
             drafter.release()
         return out[:, :int(emitted.max().item())], scores
 
-    def _speculative_device(self, input_ids, lens, logits, cache, max_new, pad, drafter):
+    def _speculative_device(self, input_ids, lens, logits, cache, max_new, pad, drafter,
+                            seed=None):
         """``_speculative`` with the verify on the device (``spec_device_loop``):
         token 0 by ``ops.select_token`` on the prefill ``logits``, then rounds
         of ``_GraphedSpecRound`` on a ``SpecState``.  With the built-in drafter
@@ -1289,9 +1400,11 @@ class GPTForGeneration(torch.nn.Module):
             input_ids, lens, logits.shape[-1], N, g + 1, eos=self.eos_token_id, pad=pad,
             min_len=self.min_length, penalty=self.repetition_penalty,
             forced_bos=self.forced_bos_token_id, forced_eos=self.forced_eos_token_id,
-            max_len=max_new)
+            max_len=max_new, greedy=seed is None, temperature=self.temperature, top_k=self.top_k,
+            top_p=self.top_p, seed=seed)
         ops.select_token(logits, state)
         state.start_window()
+        pick = None if seed is None else _CoupledPick(self, state.seed, state.step)
         builtin = drafter is self._quant_drafter
         rnd = _GraphedSpecRound(self, cache, state, builtin)
         tok = state.tok.view(B, g + 1)
@@ -1299,7 +1412,7 @@ class GPTForGeneration(torch.nn.Module):
             if r % self.spec_poll == 0 and not bool(state.any_active.item()):
                 break
             if not builtin:
-                tok[:, 1:].copy_(drafter.propose(state.nxt, state.cur, cache, g))
+                tok[:, 1:].copy_(_propose(drafter, state.nxt, state.cur, cache, g, pick))
             rnd()
         rounds, accepted, T = torch.stack([state.rounds.max().long(), state.accepted.sum(),
                                            state.finish_len.max().long()]).tolist()
@@ -1308,7 +1421,7 @@ class GPTForGeneration(torch.nn.Module):
             drafter.release()
         return state.out[:, :T], state.scores
 
-    def _device_loop(self, input_ids, lens, logits, cache, max_new, pad, gen):
+    def _device_loop(self, input_ids, lens, logits, cache, max_new, pad, gen, seed=None):
         """The sampling / greedy loop with the selection on the device
         (``device_loop``): selection 0 on the prefill ``logits``, then up to
         ``N - 1`` times {decode step -> selection}, replayed from one HIP
@@ -1322,12 +1435,12 @@ class GPTForGeneration(torch.nn.Module):
         if N == 0:
             return (torch.zeros(B, 0, dtype=torch.long, device=dev), torch.zeros(B, device=dev))
         greedy = self.decode_strategy == "greedy_search"
-        u = None if greedy else torch.rand(N, B, generator=gen, device=dev)
+        u = None if greedy or seed is not None else torch.rand(N, B, generator=gen, device=dev)
         state = ops.SelectState(
             input_ids, lens, logits.shape[-1], N, greedy=greedy, temperature=self.temperature,
             top_k=self.top_k, top_p=self.top_p, eos=eos, pad=pad, min_len=self.min_length,
             penalty=self.repetition_penalty, forced_bos=self.forced_bos_token_id,
-            forced_eos=self.forced_eos_token_id, max_len=max_new, u=u)
+            forced_eos=self.forced_eos_token_id, max_len=max_new, u=u, seed=seed)
         ops.select_token(logits, state)
         step = None
         if self.use_hip_graph and dev.type == "cuda":

@@ -10,6 +10,7 @@ from .quant import (quantize_weight_int4, dequantize_weight_int4, pack_int4,  # 
                     unpack_int4)
 from .sampling import fused_sample, select_token, SelectState  # noqa: F401
 from .sampling import spec_verify, SpecState  # noqa: F401
+from .sampling import coupled_sample, coupled_keys  # noqa: F401
 from .softmax import (fused_softmax, softmax_mask_fuse,  # noqa: F401
                       softmax_mask_fuse_upper_triangle)
 from . import _lib  # noqa: F401

@@ -6,15 +6,21 @@ The uniforms come from a torch generator so seeded generation is
 reproducible; CPU tensors take the PyTorch reference path
 (``generation.top_k_filter`` / ``top_p_filter`` + ``torch.multinomial``).
 
+``coupled_sample`` is the coupled sampler: a Gumbel race over the same kept
+set with noise that depends only on ``(seed, token index, row, vocabulary
+index)`` (``parallel.rng.coupled_noise``), so a draft model and its target draw
+token ``t`` with the same noise and speculative decoding can run under sampling.
+
 ``select_token`` is the whole per-token selection on the device (logits
 processors, pick, EOS bookkeeping; ``Generation.device_loop``) on a
-``SelectState``.  ``spec_verify`` is the verify step of a speculative greedy
+``SelectState``.  ``spec_verify`` is the verify step of a speculative
 round (per-slot processors, picks, acceptance, EOS; ``Generation.spec_device_loop``)
 on a ``SpecState``.
 """
 import torch
 
 from . import _lib
+from ..parallel import rng
 
 
 def fused_sample(logits, temperature=1.0, top_k=0, top_p=1.0, generator=None,
@@ -64,6 +70,90 @@ def fused_sample(logits, temperature=1.0, top_k=0, top_p=1.0, generator=None,
 
 
 # ---------------------------------------------------------------------------
+# the coupled sampler (coupled_sample_kernel in csrc/kernels/sampling.hip)
+# ---------------------------------------------------------------------------
+def seed_tensor(seed, device):
+    """``seed`` as the int64 device tensor [1] the kernels read: a tensor is
+    checked and kept, an int is wrapped to 64 bits."""
+    if torch.is_tensor(seed):
+        if seed.dtype != torch.int64 or seed.numel() != 1:
+            raise ValueError("the seed tensor must be int64 with one element")
+        return seed.to(device).view(1)
+    s = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return torch.tensor([s - (1 << 64) if s >= 1 << 63 else s], dtype=torch.int64, device=device)
+
+
+def coupled_keys(logits, temperature, top_k, top_p, seed, steps, rows=None, dtype=torch.float32):
+    """The race of the coupled sampler as a PyTorch formula: ``keys`` [R, V] =
+    ``logits / T + g`` on the tokens that ``top_k_filter`` / ``top_p_filter``
+    keep and ``-inf`` elsewhere, with ``g = rng.coupled_noise(seed, steps[r],
+    rows[r], V)``.  The pick is the argmax (lowest index among equal keys)."""
+    from ..models.language_model.gpt.generation import top_k_filter, top_p_filter
+    x = logits.float()
+    R, V = x.shape
+    temperature = 1.0 if temperature in (None, 0.0) else float(temperature)
+    lg = x / temperature if temperature != 1.0 else x
+    top_k = int(top_k or 0)
+    top_p = 1.0 if top_p is None else float(top_p)
+    if rows is None:
+        rows = torch.arange(R)
+    g = rng.coupled_noise(seed, steps, rows, V, device=x.device, dtype=dtype)
+    keys = lg.to(dtype) + g
+    if top_k or top_p < 1.0:
+        probs = torch.softmax(lg, -1)
+        if top_k:
+            probs = top_k_filter(probs, top_k)
+        if top_p < 1.0:
+            probs = top_p_filter(probs, top_p)
+        keys = torch.where(probs > 0, keys, torch.full_like(keys, float("-inf")))
+    return keys
+
+
+def coupled_sample(logits, temperature, top_k, top_p, seed, steps, rows=None, return_keys=False):
+    """The coupled pick of one token per row of ``logits`` [R, V] (fp32): row
+    ``r`` chooses token index ``steps[r]`` of noise row ``rows[r]`` (``r``
+    itself without ``rows``): ``argmax_i (logits[r, i] / T + g_i)`` over the
+    kept set of ``fused_sample`` with the shared noise ``g`` of
+    ``rng.coupled_noise``.  ``seed`` is an int64 device tensor [1] (an int is
+    wrapped), ``steps`` / ``rows`` int32 [R]; all three are read on the device,
+    so a captured call follows them under graph replay.
+
+    Returns ``(ids int64 [R], lse fp32 [R])`` as ``fused_sample`` does; with
+    ``return_keys`` also the formula's keys [R, V] (``coupled_keys``).  CPU
+    tensors take the formula."""
+    if logits.dim() != 2:
+        raise ValueError("coupled_sample expects [R, V] logits")
+    R, V = logits.shape
+    dev = logits.device
+    seed = seed_tensor(seed, dev)
+    steps = torch.as_tensor(steps, device=dev).to(torch.int32).reshape(-1).contiguous()
+    if rows is not None:
+        rows = torch.as_tensor(rows, device=dev).to(torch.int32).reshape(-1).contiguous()
+    if steps.numel() != R or (rows is not None and rows.numel() != R):
+        raise ValueError("coupled_sample expects %d steps and rows" % R)
+    keys = None
+    if return_keys or not logits.is_cuda:
+        keys = coupled_keys(logits, temperature, top_k, top_p, seed, steps, rows)
+    if not logits.is_cuda:
+        ids = torch.argmax(keys, -1)
+        lse = torch.logsumexp(logits.float(), -1)
+        return (ids, lse, keys) if return_keys else (ids, lse)
+    if logits.dtype != torch.float32 or logits.stride(1) != 1:
+        logits = logits.float().contiguous()
+    ids = torch.empty(R, device=dev, dtype=torch.int64)
+    lse = torch.empty(R, device=dev, dtype=torch.float32)
+    inv_t = 1.0 / float(temperature) if temperature not in (None, 0.0) else 1.0
+    rc = _lib.kernels().coupled_sample(
+        logits.data_ptr(), logits.stride(0), R, V, inv_t, int(top_k or 0),
+        float(1.0 if top_p is None else top_p), steps.data_ptr(), _lib.ptr(rows),
+        seed.data_ptr(), ids.data_ptr(), lse.data_ptr(), _lib.stream())
+    if rc != 0:
+        raise RuntimeError("coupled sampling launch failed ({})".format(rc))
+    _lib.maybe_sync()
+    return (ids, lse, keys) if return_keys else (ids, lse)
+
+
+# ---------------------------------------------------------------------------
 # on-device token selection (K18, K19; select_kernel in csrc/kernels/sampling.hip)
 # ---------------------------------------------------------------------------
 def _pack_seen(tokens, vocab):
@@ -102,7 +192,10 @@ class SelectState:
     * ``scores`` fp32 [B]; ``out`` int64 [B, n_steps];
     * ``nxt`` / ``cur`` int64 [B]: the token to embed next and its position
       ``lens + step`` -- the decode step's static inputs;
-    * ``u`` fp32 [n_steps, B]: the uniforms of a sampling run.
+    * ``u`` fp32 [n_steps, B]: the uniforms of a sampling run;
+    * ``seed`` int64 [1]: ``greedy=False`` with a ``seed`` and no ``u`` selects
+      the coupled pick (``coupled_sample`` with token index ``step`` and the
+      row's index) instead of the inverse-CDF draw.
 
     The scalars mirror ``GPTForGeneration._processors``: ``min_len`` (with an
     ``eos``), ``penalty``, ``forced_bos`` at step 0, ``forced_eos`` at step
@@ -110,7 +203,7 @@ class SelectState:
 
     def __init__(self, input_ids, lens, vocab, n_steps, greedy=True, temperature=1.0, top_k=0,
                  top_p=1.0, eos=None, pad=0, min_len=0, penalty=1.0, forced_bos=None,
-                 forced_eos=None, max_len=None, u=None):
+                 forced_eos=None, max_len=None, u=None, seed=None):
         dev = input_ids.device
         B = input_ids.shape[0]
         if not 0 <= pad < vocab:
@@ -118,8 +211,10 @@ class SelectState:
         for t in (eos, forced_bos, forced_eos):
             if t is not None and not 0 <= t < vocab:
                 raise ValueError("token %d outside the vocabulary" % t)
-        if not greedy and (u is None or tuple(u.shape) != (n_steps, B)):
+        self.coupled = not greedy and u is None and seed is not None
+        if not greedy and not self.coupled and (u is None or tuple(u.shape) != (n_steps, B)):
             raise ValueError("sampling needs uniforms u [n_steps, B]")
+        self.seed = seed_tensor(seed, dev) if self.coupled else None
         self.vocab, self.n_steps, self.greedy = vocab, n_steps, bool(greedy)
         self.temperature = 1.0 if temperature in (None, 0.0) else float(temperature)
         self.top_k = int(top_k or 0)
@@ -168,7 +263,8 @@ def processed_logits(logits, state, step=None, seen=None):
 
 def select_token(logits, state):
     """One step of token selection on the device: the logits processors, the
-    pick (greedy, or top-k / top-p sampling with ``state.u[step]``) and the
+    pick (greedy, top-k / top-p sampling with ``state.u[step]``, or the coupled
+    pick of token index ``step`` under ``state.seed``) and the
     loop's bookkeeping, all from and into ``state`` (``SelectState``); nothing
     is read back to the host, so the call can be captured into a HIP graph
     behind the decode step.  ``logits`` [B, V] fp32 is not written.
@@ -191,14 +287,15 @@ def select_token(logits, state):
             logits = logits.float().contiguous()
         none = lambda t: -1 if t is None else int(t)  # noqa: E731
         rc = _lib.kernels().select(
-            logits.data_ptr(), logits.stride(0), B, V, 0 if st.greedy else 1,
+            logits.data_ptr(), logits.stride(0), B, V,
+            0 if st.greedy else 2 if st.coupled else 1,
             1.0 / st.temperature, st.top_k, st.top_p, _lib.ptr(st.u), st.n_steps, none(st.eos),
             st.pad, st.min_len, st.penalty, st.inv_penalty, none(st.forced_bos),
             none(st.forced_eos), st.max_len - 1, st.seen.data_ptr(), st.seen.shape[1],
             st.step.data_ptr(),
             st.unfinished.data_ptr(), st.finish_len.data_ptr(), st.scores.data_ptr(),
             st.out.data_ptr(), st.nxt.data_ptr(), st.cur.data_ptr(), st.lens.data_ptr(),
-            _lib.stream())
+            _lib.stream(), _lib.ptr(st.seed))
         if rc != 0:
             raise RuntimeError("token selection launch failed ({})".format(rc))
         _lib.maybe_sync()
@@ -211,6 +308,8 @@ def select_token(logits, state):
     lse = torch.logsumexp(x, -1)
     if st.greedy:
         pick = torch.argmax(x, -1)
+    elif st.coupled:
+        pick = torch.argmax(coupled_keys(x, st.temperature, st.top_k, st.top_p, st.seed, step), -1)
     else:
         from ..models.language_model.gpt.generation import top_k_filter, top_p_filter
         probs = torch.softmax(x / st.temperature if st.temperature != 1.0 else x, -1)
@@ -245,12 +344,13 @@ def select_token(logits, state):
 
 
 # ---------------------------------------------------------------------------
-# on-device verify of speculative greedy decoding (spec_pick_kernel and
+# on-device verify of speculative decoding (spec_pick_kernel and
 # spec_accept_kernel in csrc/kernels/sampling.hip)
 # ---------------------------------------------------------------------------
 class SpecState(SelectState):
-    """``SelectState`` of a speculative greedy run (``spec_verify``), greedy
-    only.  ``step`` is the number of tokens emitted, ``nxt`` the last emitted
+    """``SelectState`` of a speculative run (``spec_verify``): greedy, or
+    with ``greedy=False`` and a ``seed`` the coupled pick (no inverse-CDF
+    draw: its uniforms cannot be shared with a drafter).  ``step`` is the number of tokens emitted, ``nxt`` the last emitted
     token and ``cur`` its position (it is not in the KV cache yet).  On top of
     the base state, with ``W = window = spec_tokens + 1``:
 
@@ -258,7 +358,7 @@ class SpecState(SelectState):
       ``b*W`` holds ``nxt[b]``, rows ``b*W + 1 ..`` the round's drafts, which
       the drafter writes; ``pos[b*W + j] = cur[b] + j``;
     * ``wlens`` int32 [B]: the keys before the window (``cur``);
-    * ``picks`` int32 [B, W] / ``logp`` fp32 [B, W]: the target's greedy pick
+    * ``picks`` int32 [B, W] / ``logp`` fp32 [B, W]: the target's pick
       of every slot and its log-probability (scratch between the two kernels);
     * ``rounds`` / ``accepted`` int32 [B]: rounds in which the row still
       emitted, and the drafts the target agreed with in them;
@@ -272,7 +372,10 @@ class SpecState(SelectState):
             raise ValueError("window must be in 1..8 (got %r)" % (window,))
         if input_ids.shape[0] > 64:
             raise ValueError("spec_verify covers at most 64 rows")
-        super().__init__(input_ids, lens, vocab, n_steps, greedy=True, **kw)
+        greedy = kw.pop("greedy", True)
+        if not greedy and (kw.get("u") is not None or kw.get("seed") is None):
+            raise ValueError("a sampling SpecState needs a seed and no uniforms")
+        super().__init__(input_ids, lens, vocab, n_steps, greedy=greedy, **kw)
         dev = input_ids.device
         B, W = input_ids.shape[0], int(window)
         self.window = W
@@ -315,7 +418,9 @@ def spec_verify(logits, state):
       max_len - 1``, never forced BOS) and the repetition penalty sees
       ``seen`` plus ``d_1 .. d_j`` (ids outside the vocabulary count as not
       seen; the bitmap itself is not touched); ``picks[j]`` is the argmax
-      (lowest index among equal maxima), ``logp[j] = x'[pick] - logsumexp(x')``.
+      (lowest index among equal maxima) or, on a coupled state, the coupled
+      pick of token index ``step + j`` in row ``b``;
+      ``logp[j] = x'[pick] - logsumexp(x')``.
       Slots at or past ``n_steps`` are picked too and never emitted;
     * ``n`` = the leading ``i`` in ``1..g`` with ``d_i == picks[i-1]``;
       ``m = min(n + 1, n_steps - step)``; an EOS among ``picks[:m]`` cuts ``m``
@@ -346,7 +451,8 @@ def spec_verify(logits, state):
             st.finish_len.data_ptr(), st.scores.data_ptr(), st.out.data_ptr(), st.nxt.data_ptr(),
             st.cur.data_ptr(), st.tok.data_ptr(), st.pos.data_ptr(), st.wlens.data_ptr(),
             st.picks.data_ptr(), st.logp.data_ptr(), st.rounds.data_ptr(),
-            st.accepted.data_ptr(), st.any_active.data_ptr(), _lib.stream())
+            st.accepted.data_ptr(), st.any_active.data_ptr(), _lib.stream(),
+            1 if st.coupled else 0, 1.0 / st.temperature, st.top_k, st.top_p, _lib.ptr(st.seed))
         if rc != 0:
             raise RuntimeError("speculative verify launch failed ({})".format(rc))
         _lib.maybe_sync()
@@ -368,7 +474,11 @@ def spec_verify(logits, state):
             seen = seen.clone()
             seen[rows[ok], d[ok, j - 1]] = True
         x = processed_logits(lg[:, j], st, step + j, seen)
-        t[:, j] = torch.argmax(x, -1)
+        if st.coupled:
+            t[:, j] = torch.argmax(coupled_keys(x, st.temperature, st.top_k, st.top_p, st.seed,
+                                                step + j), -1)
+        else:
+            t[:, j] = torch.argmax(x, -1)
         lp[:, j] = x.gather(1, t[:, j:j + 1]).squeeze(1) - torch.logsumexp(x, -1)
     st.picks.copy_(torch.where(active[:, None], t.int(), st.picks))
     st.logp.copy_(torch.where(active[:, None], lp, st.logp))

@@ -54,6 +54,54 @@ def lowbias32(x):
     return x
 
 
+def mix64(z):
+    """The splitmix64 finaliser on a Python int (``fx_mix64`` in fx_common.h)."""
+    z &= 0xFFFFFFFFFFFFFFFF
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
+    return z ^ (z >> 31)
+
+
+def coupled_key(seed, t, b):
+    """The 64-bit key of token index ``t`` in row ``b`` under ``seed`` (Python
+    ints; ``coupled_key`` in csrc/kernels/sampling.hip)."""
+    tb = ((int(t) & MASK32) << 32) | (int(b) & MASK32)
+    return mix64(mix64(int(seed) + _GOLDEN) ^ tb)
+
+
+def coupled_hash(seed, t, b, V, device="cpu"):
+    """``h`` [R, V] (int64 holding uint32): the 32-bit word of every vocabulary
+    index for the rows ``(t[r], b[r])``: ``lowbias32(lowbias32(i ^ klo) ^ khi)``
+    with the row's ``coupled_key``.  ``seed`` is an int or an int64 tensor [1],
+    ``t`` / ``b`` are ints or integer tensors [R]."""
+    seed = int(seed.item()) if torch.is_tensor(seed) else int(seed)
+    t = [int(v) for v in t.reshape(-1).tolist()] if torch.is_tensor(t) else [int(t)]
+    b = [int(v) for v in b.reshape(-1).tolist()] if torch.is_tensor(b) else [int(b)]
+    if len(t) == 1:
+        t = t * len(b)
+    if len(b) == 1:
+        b = b * len(t)
+    keys = [coupled_key(seed, ti, bi) for ti, bi in zip(t, b)]
+    klo = torch.tensor([k & MASK32 for k in keys], dtype=torch.int64, device=device)[:, None]
+    khi = torch.tensor([k >> 32 for k in keys], dtype=torch.int64, device=device)[:, None]
+    i = torch.arange(V, dtype=torch.int64, device=device)[None, :]
+    return lowbias32(lowbias32(i ^ klo) ^ khi)
+
+
+def coupled_noise(seed, t, b, V, device="cpu", dtype=torch.float32):
+    """Gumbel noise ``g`` [R, V] of the coupled sampler: a function of ``(seed,
+    t, b, i)`` alone, so whoever picks token ``t`` of row ``b`` draws with the
+    same noise.  ``U = ((h >> 9) + 0.5) * 2^-23`` (23 bits: exact in fp32, never
+    0 or 1), ``g = -log(-log(U))``, in about [-2.8, 16.6].  ``dtype`` float64
+    gives the reference of the kernel tests; ``h`` is bitwise the kernel's."""
+    return -torch.log(-torch.log(coupled_uniform(coupled_hash(seed, t, b, V, device), dtype)))
+
+
+def coupled_uniform(h, dtype=torch.float32):
+    """``U`` in (0, 1) from the 32-bit words ``h`` (int64 holding uint32)."""
+    return ((h >> 9).to(dtype) + 0.5) * (2.0 ** -23)
+
+
 def threshold16(p):
     """Drop when rand16 < thr; keep probability is 1 - thr/65536."""
     return int(round(p * 65536.0))

@@ -8,6 +8,7 @@ epilogues).  Random-init weights, bf16.
                                      [--device-loop [--repeat 3]]
                                      [--spec-draft int4_g256 --spec-tokens 2 4
                                       [--spec-device-loop]]
+                                     [--strategy sampling --sampler coupled]
 
 One JSON line per (batch, fused): ms/token, tokens/s and the effective weight
 stream rate (parameter bytes / ms per token).  ``--weight-quant int8`` / ``int4_g256`` (or
@@ -21,7 +22,10 @@ value on the 16-bit target weights, alternating likewise; its lines report ms
 per emitted token, accepted / drafted and the ms of one round (``spec_tokens``
 draft steps and one window step), to put another acceptance rate in.
 ``--spec-device-loop`` adds every speculative series once more with the verify
-on the device (``Generation.spec_device_loop``), alternating likewise."""
+on the device (``Generation.spec_device_loop``), alternating likewise.
+``--sampler coupled`` (with ``--strategy sampling``) draws with the coupled
+sampler, under which ``--spec-draft`` applies to sampling as well; every call is
+seeded, so the series of one run emit comparable text."""
 import argparse
 import json
 import os
@@ -52,6 +56,8 @@ def main():
     ap.add_argument("--spec-draft", default=None, choices=["int8", "int4_g256"],
                     help="also run speculative greedy decoding with this draft format")
     ap.add_argument("--spec-tokens", type=int, nargs="+", default=[4])
+    ap.add_argument("--sampler", default="inverse_cdf", choices=["inverse_cdf", "coupled"],
+                    help="Generation.sampler of a sampling run (top-k 50, top-p 0.75)")
     ap.add_argument("--spec-device-loop", action="store_true",
                     help="also run every speculative series with Generation.spec_device_loop")
     ap.add_argument("--repeat", type=int, default=1)
@@ -82,7 +88,8 @@ def main():
         series += [(True, wq, False, 0, False) for wq in args.weight_quant]
         if args.device_loop and args.strategy != "beam_search":
             series += [(f, wq, True, 0, False) for f, wq, _, _, _ in series if f]
-        if args.spec_draft and args.strategy == "greedy_search":
+        coupled = args.strategy == "sampling" and args.sampler == "coupled"
+        if args.spec_draft and (args.strategy == "greedy_search" or coupled):
             for k in args.spec_tokens:
                 series += [(True, None, False, k, sdl)
                            for sdl in ((False, True) if args.spec_device_loop else (False,))]
@@ -91,26 +98,30 @@ def main():
                     "decode_strategy": args.strategy, "num_beams": args.num_beams,
                     "weight_quant": wq, "device_loop": dloop,
                     "prefill_chunk": args.prefill_chunk}
+            if args.strategy == "sampling":
+                conf.update(sampler=args.sampler, top_k=50, top_p=0.75)
             if spec:
                 conf.update(spec_draft=args.spec_draft, spec_tokens=spec, spec_device_loop=sdl)
             gen = GPTForGeneration(model, conf)
-            gen.generate(prompt, max_length=8)
+            seed = {"seed": 1234} if args.strategy == "sampling" else {}
+            gen.generate(prompt, max_length=8, **seed)
             torch.cuda.synchronize()
             torch.cuda.reset_peak_memory_stats()
             base = torch.cuda.memory_allocated()
             t0 = time.perf_counter()
-            gen.generate(prompt, max_length=1)
+            gen.generate(prompt, max_length=1, **seed)
             torch.cuda.synchronize()
             t_pre = time.perf_counter() - t0
             peak = torch.cuda.max_memory_allocated() - base
             t0 = time.perf_counter()
-            ids, _ = gen.generate(prompt)
+            ids, _ = gen.generate(prompt, **seed)
             torch.cuda.synchronize()
             t = time.perf_counter() - t0
             ms = 1e3 * (t - t_pre) / max(1, ids.shape[1] - 1)
             persistent = fused and B <= 4 and \
                 os.environ.get("FLEETX_DECODE_PERSISTENT", "0") == "1"
             line = {"model": args.model, "batch": B, "strategy": args.strategy,
+                    "sampler": args.sampler if args.strategy == "sampling" else None,
                     "num_beams": args.num_beams if args.strategy == "beam_search" else 1,
                     "fused_decode": fused, "weight_quant": wq,
                     "device_loop": dloop,
