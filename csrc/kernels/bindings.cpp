@@ -182,6 +182,17 @@ PYBIND11_MODULE(_kernels, m) {
                              reinterpret_cast<const int*>(kv_lens), B, H, Sq, Sk, D, scale,
                              S(st));
   });
+  m.def("flash_fwd_qoff_split", [](int dt, ptr q, ptr k, ptr v, ptr out, ptr lse,
+                                   std::vector<long> qs, std::vector<long> ks,
+                                   std::vector<long> vs, std::vector<long> os, ptr q_starts,
+                                   ptr kv_lens, int B, int H, int Sq, int Sk, int D, float scale,
+                                   ptr ws_o, ptr ws_ml, int nsplit, int min_tiles, ptr st) {
+    auto a = v3(qs), b = v3(ks), c = v3(vs), d = v3(os);
+    return fx_flash_fwd_qoff_split(dt, CP(q), CP(k), CP(v), P(out), F(lse), a.data(), b.data(),
+                                   c.data(), d.data(), reinterpret_cast<const int*>(q_starts),
+                                   reinterpret_cast<const int*>(kv_lens), B, H, Sq, Sk, D, scale,
+                                   F(ws_o), F(ws_ml), nsplit, min_tiles, S(st));
+  });
   m.def("flash_bwd", [](int dt, ptr q, ptr k, ptr v, ptr o, ptr dout, ptr lse, ptr delta, ptr dq,
                         ptr dk,
                         ptr dv, std::vector<long> qs, std::vector<long> ks, std::vector<long> vs,

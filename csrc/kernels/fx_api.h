@@ -62,6 +62,9 @@ int fx_flash_fwd(int, const void*, const void*, const void*, void*, float*, cons
 int fx_flash_fwd_qoff(int, const void*, const void*, const void*, void*, float*, const long*,
                       const long*, const long*, const long*, const int*, const int*, int, int, int,
                       int, int, float, hipStream_t);
+int fx_flash_fwd_qoff_split(int, const void*, const void*, const void*, void*, float*, const long*,
+                            const long*, const long*, const long*, const int*, const int*, int,
+                            int, int, int, int, float, float*, float*, int, int, hipStream_t);
 int fx_flash_bwd(int, const void*, const void*, const void*, const void*, const void*, const float*,
                  float*, void*, void*, void*, const long*, const long*, const long*, const long*,
                  const long*, const long*, const int*, const float*, long, int, int, int, int, int,

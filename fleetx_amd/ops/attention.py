@@ -482,7 +482,54 @@ def _prefill_attention_formula(q, k_cache, v_cache, q_starts, kv_lens, scale):
     return torch.einsum("bhql,blhd->bqhd", p, vf).to(q.dtype), lse
 
 
-def prefill_attention(q, k_cache, v_cache, q_starts, kv_lens, scale=None, return_lse=False):
+def _prefill_tile(Sq, D):
+    """(tile width, query rows per workgroup) of the offset forward's launch
+    rows: tile 64 / 128 run 4 waves of 32 rows, tile 96 three when that leaves
+    fewer idle waves (``waves_for`` in flash_attn.hip)."""
+    dt = 64 if D <= 64 else (96 if D <= 96 else 128)
+    nw = 4
+    if dt == 96:
+        tiles = -(-Sq // 32)
+        nw = 3 if -(-Sq // 96) * 3 - tiles < -(-Sq // 128) * 4 - tiles else 4
+    return dt, 32 * nw
+
+
+PREFILL_MIN_CHUNK = 512  # keys: floor of a split in ``prefill_splits`` and in the call it serves
+
+
+def prefill_splits(B, H, Sq, maxlen, D, target_wgs=256, min_chunk=PREFILL_MIN_CHUNK):
+    """Split-K factor of ``prefill_attention``: a function of the shapes only,
+    never of the offsets or lengths, so every call on one cache shape makes the
+    same choice and a captured call replays.  ``blocks = B * H * ceil(Sq / QB)``
+    workgroups is what the unsplit kernel launches; the key axis is cut until
+    about ``target_wgs`` workgroups run (one per CU: a workgroup is 4 waves at
+    2-3 waves per SIMD), with at most ``maxlen // min_chunk`` splits.  The call
+    passes ``min_chunk // 128`` as the least number of 64-key tiles per split,
+    so short contexts in a long cache stay in few workgroups.  Caches under
+    ``2 * min_chunk`` rows and calls of ``target_wgs`` blocks or more return 1:
+    the unsplit kernel, bit for bit.
+
+    Both figures are ``beam_decode_splits``'s rule carried over and then held
+    against a sweep on the MI355X (H 32 and 16, D 128, bf16 / fp16, B 1 / 2 / 8,
+    contexts 1024-8192, blocks of 65 / 128 / 512 rows, nsplit 1 / 2 / 4 / 8 / 16
+    and this rule; medians of three, tools/bench_prefill_split.py,
+    profiles/prefill_split/README.md): in all 104 of 144 cases where the rule
+    returns more than 1 the split call with its combine pass beats the unsplit
+    kernel, by 1.1x to 6.3x, outside the unsplit kernel's own spread (at most
+    7 %).  At 256 blocks (H 32, B 8, one block per head) 2 splits cost up to
+    32 % up to 4096 keys, so ``target_wgs`` stays 256; 16 splits, which the
+    rule reaches only below 32 heads, are the best column at B 1, H 16 over
+    8192 keys.  Fewer than 16 heads, other head dims and B 2 with 512-row
+    blocks at H 32 (left at 1, where 2 splits would gain) are not tuned."""
+    qb = _prefill_tile(Sq, D)[1]
+    blocks = B * H * -(-Sq // qb)
+    if blocks <= 0:  # an empty call: nothing to split
+        return 1
+    return max(1, min(-(-target_wgs // blocks), maxlen // min_chunk))
+
+
+def prefill_attention(q, k_cache, v_cache, q_starts, kv_lens, scale=None, return_lse=False,
+                      nsplit=None, min_split_tiles=None):
     """Causal attention of a block of ``Sq`` new tokens per sample over a KV
     cache that already holds their K/V rows (forward only, bf16 / fp16 on the
     GPU): chunked prefill and the follow-up turn of a session.
@@ -499,8 +546,18 @@ def prefill_attention(q, k_cache, v_cache, q_starts, kv_lens, scale=None, return
 
     Head dims that are multiples of 8 up to 128 run ``fa_fwd_qoff_kernel`` on
     GPU tensors; anything else (CPU, other head dims) the fp32 formula, rounded
-    once at the store.  Returns O [B, Sq, H, D], with ``return_lse`` also the
-    fp32 lse [B, H, Sq]."""
+    once at the store (it ignores ``nsplit``).  Returns O [B, Sq, H, D], with
+    ``return_lse`` also the fp32 lse [B, H, Sq].
+
+    ``nsplit``: split-K factor.  1 is the single kernel above.  ``n >= 2`` cuts
+    every query block's keys into ``n`` ranges of at least ``min_split_tiles``
+    (default 1) 64-key tiles, one workgroup each
+    (``fa_fwd_qoff_split_kernel``), merged by ``fa_split_combine_kernel``: same
+    masks, same empty-row and padding-row rules, and no cache row at or past
+    ``kv_lens[b]`` is read.  ``None`` takes ``prefill_splits``, a function of
+    the shapes.  With ``nsplit > 1`` a row's bits depend on ``nsplit`` and on
+    the lengths (ranges divide the block's own extent), so the split path is
+    not slot-invariant."""
     if any(t.requires_grad for t in (q, k_cache, v_cache)):
         raise ValueError("prefill attention is forward only: an input requires grad")
     if q.dim() != 4 or k_cache.dim() != 4 or k_cache.shape != v_cache.shape \
@@ -509,6 +566,8 @@ def prefill_attention(q, k_cache, v_cache, q_starts, kv_lens, scale=None, return
     B, Sq, H, D = q.shape
     if q_starts.numel() != B or kv_lens.numel() != B:
         raise ValueError("prefill attention: q_starts and kv_lens must be [B]")
+    if (nsplit is not None and nsplit < 1) or (min_split_tiles is not None and min_split_tiles < 1):
+        raise ValueError("prefill attention: nsplit and min_split_tiles must be at least 1")
     scale = _default_scale(scale, D)
     if not q.is_cuda or not _native_dim(D):
         out, lse = _prefill_attention_formula(q, k_cache, v_cache, q_starts, kv_lens, scale)
@@ -522,11 +581,26 @@ def prefill_attention(q, k_cache, v_cache, q_starts, kv_lens, scale=None, return
     lse = torch.empty(B * H * Sq, device=q.device, dtype=torch.float32)
     qs = q_starts.to(device=q.device, dtype=torch.int32).contiguous()
     kl = kv_lens.to(device=q.device, dtype=torch.int32).contiguous()
-    rc = _lib.kernels().flash_fwd_qoff(
-        dt, q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(), lse.data_ptr(),
-        _strides(q), _strides(k_cache), _strides(v_cache), _strides(out), qs.data_ptr(),
-        kl.data_ptr(), B, H, Sq, k_cache.shape[1], D, float(scale), _lib.stream())
+    maxlen = k_cache.shape[1]
+    if B * H * Sq == 0:  # an empty call has no workspace: the unsplit entry returns at once
+        nsplit = 1
+    if nsplit is None:  # the rule, with its floor of keys per split
+        nsplit = prefill_splits(B, H, Sq, maxlen, D)
+        min_tiles = min_split_tiles or PREFILL_MIN_CHUNK // 128
+    else:
+        min_tiles = min_split_tiles or 1
+    args = (dt, q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(),
+            lse.data_ptr(), _strides(q), _strides(k_cache), _strides(v_cache), _strides(out),
+            qs.data_ptr(), kl.data_ptr(), B, H, Sq, maxlen, D, float(scale))
+    if nsplit == 1:
+        rc = _lib.kernels().flash_fwd_qoff(*args, _lib.stream())
+    else:
+        rows = B * H * nsplit * Sq
+        ws_o = torch.empty(rows * _prefill_tile(Sq, D)[0], device=q.device, dtype=torch.float32)
+        ws_ml = torch.empty(rows * 2, device=q.device, dtype=torch.float32)
+        rc = _lib.kernels().flash_fwd_qoff_split(*args, ws_o.data_ptr(), ws_ml.data_ptr(),
+                                                 int(nsplit), int(min_tiles), _lib.stream())
     if rc != 0:
-        raise RuntimeError("flash_fwd_qoff failed (%d)" % rc)
+        raise RuntimeError("flash_fwd_qoff failed (%d, nsplit %d)" % (rc, nsplit))
     _lib.maybe_sync()
     return (out, lse.view(B, H, Sq)) if return_lse else out

@@ -31,6 +31,12 @@ def main():
                     help="time ops.prefill_attention instead: S keys as chunks of CHUNK queries "
                          "over the cache (default: S in one call, and S / 4), against the plain "
                          "causal forward of S")
+    ap.add_argument("--nsplit", type=int, nargs="+", default=None, metavar="N",
+                    help="with --q-offset: the split-K factors to time for every chunk (1: the "
+                         "unsplit kernel, 0: the rule ops.attention.prefill_splits)")
+    ap.add_argument("--turn", type=int, nargs="+", default=None, metavar="ROWS",
+                    help="with --q-offset: time instead one call of ROWS queries at the end of "
+                         "a context of S keys (a session turn, a late chunk), per --nsplit")
     args = ap.parse_args()
     from fleetx_amd import ops
     B, S, H, D = args.b, args.s, args.h, args.d
@@ -72,45 +78,79 @@ def main():
                               "bwd_tflops": round(2.5 * flops / tb / 1e9, 1)}), flush=True)
 
 
+def timed(fn, iters):
+    """ms per call: ``iters`` back-to-back calls between two events, after 3 warm-up calls."""
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters
+
+
+def turn_times(ops, B, S, H, D, dt, rows, nsplits, iters, maxlen=None):
+    """One ``prefill_attention`` call of ``rows`` queries at offset S - rows of a
+    cache of ``maxlen`` (default S) rows holding S keys: {nsplit: ms}, the
+    split kernel and its combine pass together.  Key 0 is the rule; its choice
+    is returned under the key "auto"."""
+    from fleetx_amd.ops.attention import prefill_splits
+    maxlen = maxlen or S
+    q = torch.randn(B, rows, H, D, device="cuda", dtype=dt)
+    k = torch.randn(B, maxlen, H, D, device="cuda", dtype=dt)
+    v = torch.randn(B, maxlen, H, D, device="cuda", dtype=dt)
+    qs = torch.full((B,), S - rows, dtype=torch.int32, device="cuda")
+    kl = torch.full((B,), S, dtype=torch.int32, device="cuda")
+    out = {"auto": prefill_splits(B, H, rows, maxlen, D)}
+    for ns in nsplits:
+        out[ns] = timed(lambda: ops.prefill_attention(q, k, v, qs, kl, nsplit=ns or None), iters)
+    return out
+
+
 def q_offset(ops, B, S, H, D, dt, args):
     """The query-offset forward at equal work: the S x S causal triangle as
     S / CHUNK calls of CHUNK queries at offsets 0, CHUNK, ... over one cache,
     against one call of ``flash_attention``.  One JSON line per variant; the
     useful FLOPs are the triangle's in every line."""
+    from fleetx_amd.ops.attention import prefill_splits
     qkv = torch.randn(B, S, H, 3, D, device="cuda", dtype=dt)
     q, k, v = qkv.select(3, 0), qkv.select(3, 1), qkv.select(3, 2)
     flops = 2.0 * B * H * S * S * D
 
-    def timed(fn):
-        for _ in range(3):
-            fn()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(args.iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / args.iters
+    if args.turn:
+        for rows in args.turn:
+            t = turn_times(ops, B, S, H, D, dt, rows, args.nsplit or [1, 0], args.iters)
+            print(json.dumps({"B": B, "S": S, "H": H, "D": D, "dtype": args.dtype, "rows": rows,
+                              "auto_nsplit": t.pop("auto"),
+                              "ms": {str(ns): round(ms, 4) for ns, ms in t.items()}}), flush=True)
+        return
 
-    def line(name, chunk, ms):
+    def line(name, chunk, ms, **more):
         print(json.dumps({"B": B, "S": S, "H": H, "D": D, "dtype": args.dtype, "kernel": name,
                           "chunk": chunk, "calls": S // chunk, "workgroups_per_call":
                           B * H * ((-(-chunk // 128) + 1) // 2), "fwd_ms": round(ms, 4),
-                          "fwd_tflops": round(flops / ms / 1e9, 1)}), flush=True)
+                          "fwd_tflops": round(flops / ms / 1e9, 1), **more}), flush=True)
 
-    line("fa_fwd_kernel", S, timed(lambda: ops.flash_attention(q, k, v, causal=True)))
+    line("fa_fwd_kernel", S,
+         timed(lambda: ops.flash_attention(q, k, v, causal=True), args.iters))
     for chunk in (args.q_offset or [S, max(64, S // 4)]):
         if S % chunk:
             raise SystemExit("--q-offset: S must be a multiple of every chunk")
         starts = [torch.full((B,), c * chunk, dtype=torch.int32, device="cuda")
                   for c in range(S // chunk)]
         lens = [s + chunk for s in starts]
+        for ns in (args.nsplit or [1]):
+            n_run = ns or prefill_splits(B, H, chunk, S, D)
 
-        def run():
-            for c, (s, n) in enumerate(zip(starts, lens)):
-                ops.prefill_attention(q[:, c * chunk:(c + 1) * chunk], k, v, s, n)
-        line("fa_fwd_qoff_kernel", chunk, timed(run))
+            def run():
+                for c, (s, n) in enumerate(zip(starts, lens)):
+                    ops.prefill_attention(q[:, c * chunk:(c + 1) * chunk], k, v, s, n,
+                                          nsplit=ns or None)
+            line("fa_fwd_qoff_kernel" if n_run == 1 else "fa_fwd_qoff_split_kernel", chunk,
+                 timed(run, args.iters), nsplit=n_run, rule=ns == 0)
 
 
 if __name__ == "__main__":
