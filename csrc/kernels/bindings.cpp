@@ -359,6 +359,33 @@ PYBIND11_MODULE(_kernels, m) {
                              P(y), ldy, P(kc), P(vc), reinterpret_cast<const long*>(pos),
                              reinterpret_cast<const int*>(rows), heads, head_dim, maxlen, CP(ln_w), CP(ln_b), ln_eps, S(st));
   });
+  // skinny GEMM for 17..64 decode rows (decode_gemm.hip): the arguments of decode_gemv*
+  // without the LayerNorm triple, plus the launch shape (nt, ks; 0: the library's rule)
+  m.def("decode_gemm", [](int dt, int epi, int M, int N, int K, ptr x, long ldx, ptr w, long ldw,
+                          ptr bias, ptr res, long ldres, ptr y, long ldy, ptr kc, ptr vc, ptr pos,
+                          ptr rows, int heads, int head_dim, int maxlen, int nt, int ks, ptr st) {
+    return fx_decode_gemm(dt, epi, M, N, K, CP(x), ldx, CP(w), ldw, CP(bias), CP(res), ldres, P(y),
+                          ldy, P(kc), P(vc), reinterpret_cast<const long*>(pos),
+                          reinterpret_cast<const int*>(rows), heads, head_dim, maxlen, nt, ks, S(st));
+  });
+  m.def("decode_gemm_w8", [](int dt, int epi, int M, int N, int K, ptr x, long ldx, ptr wq, long ldw,
+                             ptr wscale, ptr bias, ptr res, long ldres, ptr y, long ldy, ptr kc,
+                             ptr vc, ptr pos, ptr rows, int heads, int head_dim, int maxlen, int nt,
+                             int ks, ptr st) {
+    return fx_decode_gemm_w8(dt, epi, M, N, K, CP(x), ldx, reinterpret_cast<const int8_t*>(wq), ldw,
+                             reinterpret_cast<const float*>(wscale), CP(bias), CP(res), ldres,
+                             P(y), ldy, P(kc), P(vc), reinterpret_cast<const long*>(pos),
+                             reinterpret_cast<const int*>(rows), heads, head_dim, maxlen, nt, ks, S(st));
+  });
+  m.def("decode_gemm_w4", [](int dt, int epi, int M, int N, int K, ptr x, long ldx, ptr wq, long ldw,
+                             ptr wscale, ptr bias, ptr res, long ldres, ptr y, long ldy, ptr kc,
+                             ptr vc, ptr pos, ptr rows, int heads, int head_dim, int maxlen, int nt,
+                             int ks, ptr st) {
+    return fx_decode_gemm_w4(dt, epi, M, N, K, CP(x), ldx, reinterpret_cast<const uint8_t*>(wq), ldw,
+                             reinterpret_cast<const float*>(wscale), CP(bias), CP(res), ldres,
+                             P(y), ldy, P(kc), P(vc), reinterpret_cast<const long*>(pos),
+                             reinterpret_cast<const int*>(rows), heads, head_dim, maxlen, nt, ks, S(st));
+  });
   // CU-masked stream (streams.hip): returns (stream handle, CUs selected)
   m.def("cumask_stream_create", [](int ncu) {
     int got = 0;

@@ -362,24 +362,51 @@ _LN_FUSE = os.environ.get("FLEETX_DECODE_LN_FUSE", "1") == "1"
 
 
 # weight_quant value -> (quantiser in ops, its decode GEMV in ops.gemm, k-group
-# size); a quantised copy is stored as (GEMV name, q, scale), so the format
-# travels with it
-_WEIGHT_QUANT = {"int8": ("quantize_weight_int8", "decode_linear_w8", 1),
-                 "int4_g256": ("quantize_weight_int4", "decode_linear_w4", 256)}
+# size, the GEMV's twin for 17..64 rows); a quantised copy is stored as (GEMV
+# name, q, scale), so the format travels with it
+_WEIGHT_QUANT = {"int8": ("quantize_weight_int8", "decode_linear_w8", 1, "decode_gemm_w8"),
+                 "int4_g256": ("quantize_weight_int4", "decode_linear_w4", 256, "decode_gemm_w4")}
+_ROWS_TWIN = {v[1]: v[3] for v in _WEIGHT_QUANT.values()}
 
 
 def _qlin(G, x, q8, *args, **kw):
-    """The decode GEMV of the quantised copy ``q8 = (GEMV name, q, scale)``."""
-    return getattr(G, q8[0])(x, q8[1], q8[2], *args, **kw)
+    """The decode GEMV of the quantised copy ``q8 = (GEMV name, q, scale)``, or
+    above 16 rows its skinny-GEMM twin."""
+    name = q8[0] if x.shape[0] <= 16 else _ROWS_TWIN[q8[0]]
+    return getattr(G, name)(x, q8[1], q8[2], *args, **kw)
+
+
+def _ulin(G, x, lin, epi, res=None, qkv_cache=None):
+    """One decode GEMM of ``lin`` unfused, as the unfused layer runs it: the
+    vendor GEMM with bias, then the separate GeLU / residual / K/V append."""
+    y = F.linear(x, lin.weight, lin.bias)
+    if epi == G.GV_GELU:
+        return F.gelu(y, approximate="tanh")
+    if epi == G.GV_RES:
+        return y + res
+    if epi == G.GV_QKV:
+        kc, vc, pos = qkv_cache[:3]
+        qkv5 = y.view(y.shape[0], kc.shape[2], 3, kc.shape[3])
+        ar = qkv_cache[3].long() if len(qkv_cache) > 3 else torch.arange(y.shape[0], device=y.device)
+        kc[ar, pos] = qkv5[:, :, 1]
+        vc[ar, pos] = qkv5[:, :, 2]
+        return qkv5[:, :, 0].reshape(y.shape[0], -1)
+    return y
 
 
 def _dlin(G, x, lin, epi, q8, **kw):
     """One decode GEMV of ``lin``: on its quantised copy ``q8`` where there is
-    one and its kernel covers the call, else on the 16-bit weight."""
+    one and its kernel covers the call, else on the 16-bit weight.  Above 16
+    rows the kernels are the skinny GEMM (no ``ln``), whose launch rule leaves
+    the shapes it measured slower to the vendor GEMM: that one call then runs
+    unfused (``_ulin``), so the result is never None."""
     if q8 is not None:
         y = _qlin(G, x, q8, lin.bias, epi, **kw)
         if y is not None:
             return y
+    if x.shape[0] > 16:
+        y = G.decode_gemm(x, lin.weight, lin.bias, epi, **kw)
+        return y if y is not None else _ulin(G, x, lin, epi, **kw)
     return G.decode_linear(x, lin.weight, lin.bias, epi, **kw)
 
 
@@ -390,8 +417,10 @@ def _layer_decode_fused(layer, x, cache, li, pos, lens_after, w8=None, rows=None
     GEMV + bias + residual] -> [LN2 + FFN1 GEMV + bias + GeLU] -> [FFN2 GEMV +
     bias + residual].  The LayerNorms run as GEMV prologues (each block
     normalises the few rows into LDS); shapes the fused prologue does not
-    cover fall back to a separate LayerNorm launch.  Returns None when a GEMV
-    does not cover the shape (batch > 16).  ``w8`` (``weight_quant``) maps
+    cover fall back to a separate LayerNorm launch; above 16 rows
+    (``fused_decode_rows: 64``) the GEMVs are the skinny GEMM, which has no
+    prologue, and a call it leaves to the vendor GEMM runs unfused on its own.
+    Returns None when a GEMV does not cover the shape (up to 16 rows).  ``w8`` (``weight_quant``) maps
     ``qkv_proj`` / ``out_proj`` / ``fc1`` / ``fc2`` to this layer's quantised copies.
     Window form (``rows`` int32 [B*W]): the QKV epilogue appends row ``m`` to
     ``cache[rows[m], pos[m]]`` and the attention is the window kernel with
@@ -402,8 +431,9 @@ def _layer_decode_fused(layer, x, cache, li, pos, lens_after, w8=None, rows=None
     B, h = x.shape[0], x.shape[-1]
     x2d = x.reshape(B, h)
     kv = _gen_kv(cache, li) + ((pos,) if rows is None else (pos, rows))
+    ln_fuse = _LN_FUSE and B <= 16
     q = _dlin(G, x2d, attn.qkv_proj, G.GV_QKV, w8.get("qkv_proj"), qkv_cache=kv,
-              ln=(layer.ln1.weight, layer.ln1.bias, layer.ln1.eps)) if _LN_FUSE else None
+              ln=(layer.ln1.weight, layer.ln1.bias, layer.ln1.eps)) if ln_fuse else None
     if q is None:
         q = _dlin(G, layer.ln1(x2d), attn.qkv_proj, G.GV_QKV, w8.get("qkv_proj"), qkv_cache=kv)
     if q is None:
@@ -415,7 +445,7 @@ def _layer_decode_fused(layer, x, cache, li, pos, lens_after, w8=None, rows=None
                                         lens_after)
     x2 = _dlin(G, o.view(B, -1), attn.out_proj, G.GV_RES, w8.get("out_proj"), res=x2d)
     f = _dlin(G, x2, mlp.fc1, G.GV_GELU, w8.get("fc1"),
-              ln=(layer.ln2.weight, layer.ln2.bias, layer.ln2.eps)) if _LN_FUSE else None
+              ln=(layer.ln2.weight, layer.ln2.bias, layer.ln2.eps)) if ln_fuse else None
     if f is None:
         f = _dlin(G, layer.ln2(x2), mlp.fc1, G.GV_GELU, w8.get("fc1"))
     out = _dlin(G, f, mlp.fc2, G.GV_RES, w8.get("fc2"), res=x2)
@@ -685,6 +715,12 @@ class GPTForGeneration(torch.nn.Module):
         self.use_hip_graph = bool(c.get("use_hip_graph", True))
         # decode layers as five fused kernels with weight-streaming GEMVs (K19)
         self.fused_decode = bool(c.get("fused_decode", True))
+        # most rows (batch, batch * beams, batch * window) the fused layer takes: 16, the
+        # decode GEMV alone, or 64, with the skinny GEMM (ops.gemm.decode_gemm*) above 16
+        self.fused_decode_rows = c.get("fused_decode_rows", 16)
+        if type(self.fused_decode_rows) is not int or self.fused_decode_rows not in (16, 64):
+            raise ValueError("fused_decode_rows must be 16 or 64 (got %r)"
+                             % (self.fused_decode_rows,))
         self.length_penalty = c.get("length_penalty", 0.0)
         self.early_stopping = bool(c.get("early_stopping", False))
         # weight-only int8 / int4 copies of the decode GEMV weights (None: 16-bit weights)
@@ -830,7 +866,7 @@ class GPTForGeneration(torch.nn.Module):
         def copies(fmt):
             if fmt is None:
                 return None
-            quantiser, gemv, group = _WEIGHT_QUANT[fmt]
+            quantiser, gemv, group = _WEIGHT_QUANT[fmt][:3]
 
             def quant(w):
                 if w.shape[1] % group:
@@ -888,7 +924,7 @@ class GPTForGeneration(torch.nn.Module):
         x = ops.embedding(nxt[:, None], self.gpt.embeddings.word_embeddings.weight,
                           pos[:, None], self.gpt.embeddings.position_embeddings, 0) \
             if topo.mp_world_size() == 1 else self.gpt.embeddings(nxt[:, None], pos[:, None])
-        fused = self.fused_decode and x.is_cuda and x.shape[0] <= 16
+        fused = self.fused_decode and x.is_cuda and x.shape[0] <= self.fused_decode_rows
         w8 = q8["layers"] if q8 is not None else None
         for li, layer in enumerate(self.gpt.layers):
             if fused and _fusable(layer):
@@ -907,8 +943,11 @@ class GPTForGeneration(torch.nn.Module):
         logits = None
         if self.fused_decode and topo.mp_world_size() == 1:
             from ....ops import gemm as G
-            if q8 is not None:
-                logits = _qlin(G, h.contiguous(), q8)
+            if h.shape[0] <= self.fused_decode_rows:
+                if q8 is not None:
+                    logits = _qlin(G, h.contiguous(), q8)
+                if logits is None and h.shape[0] > 16:
+                    logits = G.decode_gemm(h.contiguous(), w)
             if logits is None:
                 logits = G.decode_linear(h.contiguous(), w)
         if logits is None:
@@ -1217,9 +1256,9 @@ class GPTForGeneration(torch.nn.Module):
         reason = None
         if topo.mp_world_size() != 1:
             reason = "tensor parallelism"
-        elif batch * (self.spec_tokens + 1) > 16:
-            reason = "batch * (spec_tokens + 1) = %d rows exceed the 16 of the decode GEMV" \
-                % (batch * (self.spec_tokens + 1))
+        elif batch * (self.spec_tokens + 1) > self.fused_decode_rows:
+            reason = "batch * (spec_tokens + 1) = %d rows exceed the %d of the decode GEMV" \
+                % (batch * (self.spec_tokens + 1), self.fused_decode_rows)
         elif self._drafter is None and (dev.type != "cuda" or not self.fused_decode):
             reason = "the quantised draft needs a GPU and fused_decode"
         if reason is not None:

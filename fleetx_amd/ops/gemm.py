@@ -554,3 +554,103 @@ def decode_linear_w4(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, qkv_cache=
     if wscale is None:
         return None
     return _decode_gemv(x, wq, wscale, bias, epi, res, qkv_cache, ln, int4=True)
+
+
+# ----------------------------------------------------------------------------
+# the same for 17..64 rows (csrc/kernels/decode_gemm.hip: a register-tiled
+# skinny GEMM over the same weight stream, same weight formats and epilogues)
+# ----------------------------------------------------------------------------
+def _decode_gemm(x, w, wscale, bias, epi, res, qkv_cache, shape, int4=False):
+    """The body of ``decode_gemm`` / ``decode_gemm_w8`` / ``decode_gemm_w4``,
+    after ``_decode_gemv``: the checks, the QKV unpacking, the output and the
+    call.  None for a call the kernel does not cover; malformed caches /
+    residual assert."""
+    if not x.is_cuda or x.dim() != 2 or x.shape[0] < 17 or x.shape[0] > 64 \
+            or x.dtype not in (torch.bfloat16, torch.float16):
+        return None
+    M, K = x.shape
+    wdtype = x.dtype if wscale is None else torch.uint8 if int4 else torch.int8
+    if w.dim() != 2 or w.dtype != wdtype or not w.is_cuda or w.shape[1] * (2 if int4 else 1) != K:
+        return None
+    N = w.shape[0]
+    if w.stride(1) != 1 or x.stride(1) != 1 or K % 1024 or x.stride(0) % 8 \
+            or (w.stride(0) * w.element_size()) % 16 or w.data_ptr() % 16 or x.data_ptr() % 16:
+        return None
+    if wscale is not None and (wscale.dtype != torch.float32 or not wscale.is_cuda
+                               or (wscale.shape != (K // 256, N) if int4
+                                   else wscale.numel() != N)
+                               or not wscale.is_contiguous()):
+        return None
+    if bias is not None and (bias.dtype != x.dtype or bias.numel() != N
+                             or not bias.is_contiguous()):
+        return None
+    k = _lib.kernels()
+    kc = vc = pos = rows = None
+    heads = hd = maxlen = 0
+    if epi == GV_QKV:
+        kc, vc, pos = qkv_cache[:3]
+        rows = qkv_cache[3] if len(qkv_cache) > 3 else None
+        maxlen, heads, hd = kc.shape[1], kc.shape[2], kc.shape[3]
+        assert N == 3 * heads * hd and kc.is_contiguous() and vc.is_contiguous()
+        assert kc.shape == vc.shape and kc.dtype == x.dtype == vc.dtype
+        assert pos.dtype == torch.int64 and pos.numel() == M and pos.is_contiguous()
+        if rows is None:
+            assert kc.shape[0] >= M
+        else:
+            # rows.max() < kc.shape[0] is the caller's to keep (no sync to check it)
+            assert rows.dtype == torch.int32 and rows.numel() == M and rows.is_contiguous() \
+                and rows.is_cuda
+        y = torch.empty(M, heads * hd, device=x.device, dtype=x.dtype)
+    else:
+        y = torch.empty(M, N, device=x.device, dtype=x.dtype)
+    if epi == GV_RES:
+        assert res is not None and res.shape == (M, N) and res.stride(1) == 1 \
+            and res.dtype == x.dtype
+    nt, ks = shape if shape is not None else (0, 0)
+    head = (_lib.dt_code(x.dtype), int(epi), M, N, K, x.data_ptr(), x.stride(0),
+            w.data_ptr(), w.stride(0))
+    tail = (_lib.ptr(bias), _lib.ptr(res) if epi == GV_RES else 0,
+            res.stride(0) if epi == GV_RES else 0, y.data_ptr(), y.stride(0),
+            _lib.ptr(kc), _lib.ptr(vc), _lib.ptr(pos), _lib.ptr(rows), heads, hd, maxlen,
+            int(nt), int(ks), _lib.stream())
+    if wscale is None:
+        nb = k.decode_gemm(*head, *tail)
+    elif int4:
+        nb = k.decode_gemm_w4(*head, wscale.data_ptr(), *tail)
+    else:
+        nb = k.decode_gemm_w8(*head, wscale.data_ptr(), *tail)
+    if nb == 0:
+        return None
+    _lib.maybe_sync()
+    return y
+
+
+def decode_gemm(x, weight, bias=None, epi=GV_BIAS, res=None, qkv_cache=None, shape=None):
+    """``decode_linear`` for 17 <= M <= 64 rows: ``x [M, K] @ weight[N, K]^T``
+    on the register-tiled skinny GEMM, which streams the weight once for all
+    rows, with the same epilogues ``epi`` and the same ``qkv_cache`` forms and
+    trust rules.  There is no LayerNorm prologue: the caller normalises ``x``.
+    The bits of an output row depend on that row of ``x`` alone, not on its
+    index, on M or on the other rows.
+
+    ``shape = (nt, ks)`` pins the launch shape (16 * nt columns per block, ks
+    waves over K) for tests and ``tools/bench_gemv.py``; None: the library's rule.
+
+    Returns the output, or None when the kernel does not cover the call (the
+    caller then uses the general GEMM)."""
+    return _decode_gemm(x, weight, None, bias, epi, res, qkv_cache, shape)
+
+
+def decode_gemm_w8(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, qkv_cache=None, shape=None):
+    """``decode_gemm`` with the weight-only int8 weight of ``decode_linear_w8``."""
+    if wscale is None:
+        return None
+    return _decode_gemm(x, wq, wscale, bias, epi, res, qkv_cache, shape)
+
+
+def decode_gemm_w4(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, qkv_cache=None, shape=None):
+    """``decode_gemm`` with the weight-only int4 weight (group size 256) of
+    ``decode_linear_w4``."""
+    if wscale is None:
+        return None
+    return _decode_gemm(x, wq, wscale, bias, epi, res, qkv_cache, shape, int4=True)

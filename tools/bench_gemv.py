@@ -5,12 +5,17 @@ hipBLASLt (F.linear) on the same operands.
     python tools/bench_gemv.py [--m 1 8 16]
     python tools/bench_gemv.py --w8 [--m 1 4 16] [--repeat 2]
     python tools/bench_gemv.py --w4 [--m 1 4 16] [--repeat 2]
+    python tools/bench_gemv.py --rows 17 32 48 64 [--shape nt,ks | --sweep]
 
 ``--w8`` times the weight-only int8 GEMV (csrc/kernels/decode_gemv_w8.hip)
 against the 16-bit one, alternating in one process on weights streamed from
 HBM (each series replayed from a HIP graph, so the figure is GPU time); ``--repeat`` runs each series that many times.
 ``--w4`` does the same for the int4 GEMV with group scales
-(csrc/kernels/decode_gemv_w4.hip); its records carry ``gemv_w4_us``."""
+(csrc/kernels/decode_gemv_w4.hip); its records carry ``gemv_w4_us``.
+``--rows`` times the skinny GEMM of 17..64 rows (csrc/kernels/decode_gemm.hip)
+in its three formats against the chain it replaces (the vendor GEMM with bias
+and the layer's separate GeLU / residual launch), the same way; ``--shape``
+pins its launch shape and ``--sweep`` times every shape the library has."""
 import argparse
 import json
 import os
@@ -24,7 +29,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 SHAPES = {"1.3B_qkv": (6144, 2048), "1.3B_out": (2048, 2048), "1.3B_fc1": (8192, 2048),
           "1.3B_fc2": (2048, 8192), "6.7B_qkv": (12288, 4096), "6.7B_out": (4096, 4096),
           "6.7B_fc1": (16384, 4096), "6.7B_fc2": (4096, 16384), "lm_head_1.3B": (50304, 2048),
-          "lm_head_6.7B": (50304, 4096)}
+          "lm_head_6.7B": (50304, 4096), "345M_qkv": (3072, 1024), "345M_out": (1024, 1024),
+          "345M_fc1": (4096, 1024), "345M_fc2": (1024, 4096), "lm_head_345M": (50304, 1024)}
 
 
 def timeit(fn, iters=200):
@@ -90,6 +96,50 @@ def main_w8(args, G):
         torch.cuda.empty_cache()
 
 
+def main_rows(args, G):
+    """The skinny GEMM at ``--rows`` against the unfused chain of the same call."""
+    from fleetx_amd import ops
+    pins = [tuple(int(v) for v in args.shape.split(","))] if args.shape else [None]
+    if args.sweep:
+        pins = [(nt, ks) for nt in (1, 2, 4) for ks in (4, 8)]
+    for name in args.shapes or SHAPES:
+        N, K = SHAPES[name]
+        ncopy = max(2, -(-(1 << 30) // (N * K * 2)))
+        ws = [(torch.randn(N, K, device="cuda") * K ** -0.5).bfloat16() for _ in range(ncopy)]
+        q8 = [ops.quantize_weight_int8(w) for w in ws]
+        q4 = [ops.quantize_weight_int4(w) for w in ws]
+        b = torch.randn(N, device="cuda").bfloat16()
+        epi = G.GV_GELU if "fc1" in name else G.GV_RES if "out" in name or "fc2" in name \
+            else G.GV_BIAS
+        for M in args.rows:
+            x = torch.randn(M, K, device="cuda").bfloat16()
+            res = torch.randn(M, N, device="cuda").bfloat16() if epi == G.GV_RES else None
+
+            def chain(i):
+                y = F.linear(x, ws[i], b)
+                if epi == G.GV_GELU:
+                    y = F.gelu(y, approximate="tanh")
+                elif epi == G.GV_RES:
+                    y = y + res
+                return y
+            # every series --repeat times, the series alternating within a repeat
+            rec = {"shape": name, "M": M, "N": N, "K": K, "epi": epi, "chain_us": []}
+            for _ in range(args.repeat):
+                rec["chain_us"].append(round(time_graph(chain, ncopy), 2))
+                for pin in pins:
+                    kw = dict(epi=epi, res=res, shape=pin)
+                    for tag, f in (("w16", lambda i: G.decode_gemm(x, ws[i], b, **kw)),
+                                   ("w8", lambda i: G.decode_gemm_w8(x, *q8[i], b, **kw)),
+                                   ("w4", lambda i: G.decode_gemm_w4(x, *q4[i], b, **kw))):
+                        if f(0) is None:    # not covered, or the rule leaves it to the chain
+                            continue
+                        key = "%s_%s_us" % (tag, "rule" if pin is None else "%d_%d" % pin)
+                        rec.setdefault(key, []).append(round(time_graph(f, ncopy), 2))
+            print(json.dumps(rec), flush=True)
+        del ws, q8, q4
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--m", type=int, nargs="+", default=[1, 16])
@@ -99,8 +149,14 @@ def main():
     ap.add_argument("--w4", action="store_true", help="16-bit vs weight-only int4 (g256) GEMV")
     ap.add_argument("--repeat", type=int, default=2, help="--w8 / --w4: runs of each series")
     ap.add_argument("--shapes", nargs="+", default=None, choices=sorted(SHAPES))
+    ap.add_argument("--rows", type=int, nargs="+", default=None,
+                    help="time the 17..64-row skinny GEMM at these row counts")
+    ap.add_argument("--shape", default=None, help="--rows: pin the launch shape, nt,ks")
+    ap.add_argument("--sweep", action="store_true", help="--rows: every launch shape")
     args = ap.parse_args()
     from fleetx_amd.ops import gemm as G
+    if args.rows:
+        return main_rows(args, G)
     if args.w8 or args.w4:
         return main_w8(args, G)
     for name, (N, K) in SHAPES.items():

@@ -70,6 +70,8 @@ def main():
                          "transcript again without a session")
     ap.add_argument("--turn-tokens", type=int, default=64)
     ap.add_argument("--max-pos", type=int, default=1024, help="max_position_embeddings")
+    ap.add_argument("--fused-decode-rows", type=int, default=16, choices=[16, 64],
+                    help="Generation.fused_decode_rows: 64 keeps 17..64 rows on the fused layer")
     args = ap.parse_args()
     from fleetx_amd.models.language_model.gpt.model import GPTConfig, GPTForPretraining
     from fleetx_amd.models.language_model.gpt.generation import GPTForGeneration
@@ -97,6 +99,7 @@ def main():
             conf = {"max_dec_len": args.tokens, "fused_decode": fused,
                     "decode_strategy": args.strategy, "num_beams": args.num_beams,
                     "weight_quant": wq, "device_loop": dloop,
+                    "fused_decode_rows": args.fused_decode_rows,
                     "prefill_chunk": args.prefill_chunk}
             if args.strategy == "sampling":
                 conf.update(sampler=args.sampler, top_k=50, top_p=0.75)
@@ -123,7 +126,8 @@ def main():
             line = {"model": args.model, "batch": B, "strategy": args.strategy,
                     "sampler": args.sampler if args.strategy == "sampling" else None,
                     "num_beams": args.num_beams if args.strategy == "beam_search" else 1,
-                    "fused_decode": fused, "weight_quant": wq,
+                    "fused_decode": fused, "fused_decode_rows": args.fused_decode_rows,
+                    "weight_quant": wq,
                     "device_loop": dloop,
                     "persistent_layers": persistent,
                     "ms_per_token": round(ms, 3),
