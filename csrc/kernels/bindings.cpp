@@ -359,6 +359,18 @@ PYBIND11_MODULE(_kernels, m) {
                              P(y), ldy, P(kc), P(vc), reinterpret_cast<const long*>(pos),
                              reinterpret_cast<const int*>(rows), heads, head_dim, maxlen, CP(ln_w), CP(ln_b), ln_eps, S(st));
   });
+  // the same with packed MXFP4 weights (ldw in bytes) and one e8m0 scale byte per (row, 32 k),
+  // [N, K / 32] in the kernel's block order (decode_gemv_mx4.hip)
+  m.def("decode_gemv_mx4", [](int dt, int epi, int M, int N, int K, ptr x, long ldx, ptr wq, long ldw,
+                              ptr wscale, ptr bias, ptr res, long ldres, ptr y, long ldy, ptr kc,
+                              ptr vc, ptr pos, ptr rows, int heads, int head_dim, int maxlen,
+                              ptr ln_w, ptr ln_b, float ln_eps, ptr st) {
+    return fx_decode_gemv_mx4(dt, epi, M, N, K, CP(x), ldx, reinterpret_cast<const uint8_t*>(wq), ldw,
+                              reinterpret_cast<const uint8_t*>(wscale), CP(bias), CP(res), ldres,
+                              P(y), ldy, P(kc), P(vc), reinterpret_cast<const long*>(pos),
+                              reinterpret_cast<const int*>(rows), heads, head_dim, maxlen, CP(ln_w),
+                              CP(ln_b), ln_eps, S(st));
+  });
   // skinny GEMM for 17..64 decode rows (decode_gemm.hip): the arguments of decode_gemv*
   // without the LayerNorm triple, plus the launch shape (nt, ks; 0: the library's rule)
   m.def("decode_gemm", [](int dt, int epi, int M, int N, int K, ptr x, long ldx, ptr w, long ldw,
@@ -385,6 +397,15 @@ PYBIND11_MODULE(_kernels, m) {
                              reinterpret_cast<const float*>(wscale), CP(bias), CP(res), ldres,
                              P(y), ldy, P(kc), P(vc), reinterpret_cast<const long*>(pos),
                              reinterpret_cast<const int*>(rows), heads, head_dim, maxlen, nt, ks, S(st));
+  });
+  m.def("decode_gemm_mx4", [](int dt, int epi, int M, int N, int K, ptr x, long ldx, ptr wq, long ldw,
+                              ptr wscale, ptr bias, ptr res, long ldres, ptr y, long ldy, ptr kc,
+                              ptr vc, ptr pos, ptr rows, int heads, int head_dim, int maxlen, int nt,
+                              int ks, ptr st) {
+    return fx_decode_gemm_mx4(dt, epi, M, N, K, CP(x), ldx, reinterpret_cast<const uint8_t*>(wq), ldw,
+                              reinterpret_cast<const uint8_t*>(wscale), CP(bias), CP(res), ldres,
+                              P(y), ldy, P(kc), P(vc), reinterpret_cast<const long*>(pos),
+                              reinterpret_cast<const int*>(rows), heads, head_dim, maxlen, nt, ks, S(st));
   });
   // CU-masked stream (streams.hip): returns (stream handle, CUs selected)
   m.def("cumask_stream_create", [](int ncu) {

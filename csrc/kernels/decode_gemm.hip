@@ -5,7 +5,8 @@
 // step is still bound by the weight stream, so the weights are streamed once,
 // straight to VGPRs, and every weight operand is reused from registers by all
 // row tiles.  Weight operands: 16-bit, int8 with a scale per output row, int4
-// (decode_gemv_w4.hip's packing) with a scale per (group of 256 k, output row).
+// (decode_gemv_w4.hip's packing) with a scale per (group of 256 k, output row),
+// MXFP4 (decode_gemv_mx4.hip's packing) with an e8m0 scale per (row, 32 k).
 //
 // Register tiling:
 //  * a block owns 16 * NT output columns (rows of W) and all 16 * MT x rows,
@@ -32,6 +33,11 @@
 //    int4: a group is one scale group (PB = 4 chunks = 256 k), summed from
 //    C = 0 per (nt, mt) tile and entered as fma(sum, scale / 16, acc), with the
 //    group's scales loaded ahead of its chunks;
+//    MXFP4: the hardware conversion applies the scale to the operand, so the
+//    MFMAs go straight into acc -- one fp32 tile per (nt, mt), which admits
+//    the 4 x 4 tile int4 has no registers for.  A lane's 16 k of a chunk lie
+//    in one scale group; a loop group is 256 k (PB = 4) and the 16 scale bytes
+//    of its 512-k block are one load per weight row, taken a loop group ahead;
 //  * x is not staged in LDS: every wave reads a different K range, nothing is
 //    shared inside a block;
 //  * the wave partials are summed through LDS in NT rounds of 16 columns (KS *
@@ -70,7 +76,8 @@ struct G16 {
   typedef uint16_t elt;
   struct raw { short8 v[2]; };
   static constexpr int PACK = 1, PB = 2, FMT = 0;
-  static constexpr bool SCALED = false, GROUPED = false;
+  static constexpr bool SCALED = false, GROUPED = false, OPSCALED = false;
+  typedef float sc;
   static __device__ __forceinline__ raw load(const elt* p) {
     const short8* q = reinterpret_cast<const short8*>(p);
     raw o;
@@ -89,7 +96,8 @@ struct G8 {
   typedef int8_t elt;
   typedef uintx4 raw;
   static constexpr int PACK = 1, PB = 2, FMT = 1;
-  static constexpr bool SCALED = true, GROUPED = false;
+  static constexpr bool SCALED = true, GROUPED = false, OPSCALED = false;
+  typedef float sc;
   static __device__ __forceinline__ raw load(const elt* p) {
     return __builtin_nontemporal_load(reinterpret_cast<const uintx4*>(p));
   }
@@ -104,7 +112,8 @@ struct G4 {
   typedef uint8_t elt;
   typedef uintx2 raw;
   static constexpr int PACK = 2, PB = 4, FMT = 2;
-  static constexpr bool SCALED = false, GROUPED = true;
+  static constexpr bool SCALED = false, GROUPED = true, OPSCALED = false;
+  typedef float sc;
   static __device__ __forceinline__ raw load(const elt* p) {
     return __builtin_nontemporal_load(reinterpret_cast<const uintx2*>(p));
   }
@@ -117,11 +126,30 @@ struct G4 {
   }
 };
 
+// MXFP4 (decode_gemv_mx4.hip): a dword is 8 weights in k order, byte j = weights
+// 2j, 2j + 1; OPSCALED: ops() takes the fp32 scale of the lane's group.  It
+// shares int4's column of the launch table until its own sweep is taken.
+struct GM4 {
+  typedef uint8_t elt;
+  typedef uintx2 raw;
+  typedef uint8_t sc;
+  static constexpr int PACK = 2, PB = 4, FMT = 2;
+  static constexpr bool SCALED = false, GROUPED = false, OPSCALED = true;
+  static __device__ __forceinline__ raw load(const elt* p) {
+    return __builtin_nontemporal_load(reinterpret_cast<const uintx2*>(p));
+  }
+  template <typename T>
+  static __device__ __forceinline__ void ops(const raw& v, float s, short8 (&a)[2]) {
+    a[0] = mx4_cvt8<T>(v.x, s);
+    a[1] = mx4_cvt8<T>(v.y, s);
+  }
+};
+
 template <typename W>
 struct GemmArgs {
   const uint16_t* x;
   const typename W::elt* w;
-  const float* scale;  // G8: [N]; G4: [K / 256, N]
+  const typename W::sc* scale;  // G8: [N]; G4: [K / 256, N]; GM4: [N, K / 32] bytes
   const uint16_t* bias;
   const uint16_t* res;
   uint16_t* y;
@@ -206,6 +234,21 @@ __global__ __launch_bounds__(64 * KS) DG_NO_PK32 void decode_gemm_kernel(GemmArg
   floatx4 sv[W::GROUPED ? NT : 1];
   const float* sp = nullptr;
   if constexpr (W::GROUPED) sp = a.scale + (long)(kb / 256) * a.N;
+  // OPSCALED: per weight row the 16 scale bytes of a 512-k block (dword i:
+  // chunk i of either 256-k half) of this loop group (ev) and the next (en),
+  // and the lane's byte in a dword: 2 * (half of the block) + g / 2
+  uintx4 ev[W::OPSCALED ? NT : 1], en[W::OPSCALED ? NT : 1];
+  const uint8_t* ep[W::OPSCALED ? NT : 1];
+  int q0 = 0;  // the wave's first loop group in units of 256 k
+  if constexpr (W::OPSCALED) {
+    q0 = kb / 256;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+      ep[nt] = reinterpret_cast<const uint8_t*>(a.scale) +
+               (long)min(n0 + 16 * nt + r, a.N - 1) * (a.K / 32);
+      en[nt] = *reinterpret_cast<const uintx4*>(ep[nt] + (q0 >> 1) * 16);
+    }
+  }
   const int nb = kw / DG_CHUNK;
 
 #define DG_LOAD(S, c)                                                        \
@@ -218,22 +261,26 @@ __global__ __launch_bounds__(64 * KS) DG_NO_PK32 void decode_gemm_kernel(GemmArg
       xv[S][mt][1] = p[1];                                                   \
     }                                                                        \
   } while (0)
-#define DG_MMA(S, dst)                                                       \
+#define DG_MMA(S, I, dst)                                                    \
   do {                                                                       \
     _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) {                      \
       short8 av[2];                                                          \
-      W::template ops<T>(wv[S][nt], av);                                     \
+      if constexpr (W::OPSCALED)                                             \
+        W::template ops<T>(wv[S][nt], mx4_scale(ev[nt][I] >> esh), av);      \
+      else                                                                   \
+        W::template ops<T>(wv[S][nt], av);                                   \
       _Pragma("unroll") for (int i = 0; i < 2; ++i)                          \
           _Pragma("unroll") for (int mt = 0; mt < MT; ++mt)                  \
               dst[nt][mt] = mma16<T>(av[i], xv[S][mt][i], dst[nt][mt]);      \
     }                                                                        \
   } while (0)
-// chunk c on set S; chunk c + 1 is loaded into the other set first
-#define DG_STEP(S, c, NEXT)                                                  \
+// chunk c (the I-th of its loop group) on set S; chunk c + 1 is loaded into the
+// other set first
+#define DG_STEP(S, I, c, NEXT)                                               \
   do {                                                                       \
     if (NEXT) DG_LOAD(1 - S, (c) + 1);                                       \
-    if constexpr (W::GROUPED) DG_MMA(S, t);                                  \
-    else DG_MMA(S, acc);                                                     \
+    if constexpr (W::GROUPED) DG_MMA(S, I, t);                               \
+    else DG_MMA(S, I, acc);                                                  \
   } while (0)
 // PB chunks from c (set 0 holds chunk c); MORE: chunk c + PB exists
 #define DG_GROUP(c, MORE)                                                    \
@@ -247,13 +294,23 @@ __global__ __launch_bounds__(64 * KS) DG_NO_PK32 void decode_gemm_kernel(GemmArg
       }                                                                      \
       sp += a.N;                                                             \
     }                                                                        \
-    DG_STEP(0, c, true);                                                     \
+    int esh = 0;                                                             \
+    if constexpr (W::OPSCALED) {                                             \
+      const int q = q0 + (c) / W::PB;                                        \
+      esh = 16 * (q & 1) + 8 * (g >> 1);                                     \
+      _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) {                    \
+        ev[nt] = en[nt];                                                     \
+        if (MORE)                                                            \
+          en[nt] = *reinterpret_cast<const uintx4*>(ep[nt] + ((q + 1) >> 1) * 16); \
+      }                                                                      \
+    }                                                                        \
+    DG_STEP(0, 0, c, true);                                                  \
     if constexpr (W::PB == 4) {                                              \
-      DG_STEP(1, (c) + 1, true);                                             \
-      DG_STEP(0, (c) + 2, true);                                             \
-      DG_STEP(1, (c) + 3, MORE);                                             \
+      DG_STEP(1, 1, (c) + 1, true);                                          \
+      DG_STEP(0, 2, (c) + 2, true);                                          \
+      DG_STEP(1, 3, (c) + 3, MORE);                                          \
     } else {                                                                 \
-      DG_STEP(1, (c) + 1, MORE);                                             \
+      DG_STEP(1, 1, (c) + 1, MORE);                                          \
     }                                                                        \
     if constexpr (W::GROUPED) {                                              \
       _Pragma("unroll") for (int nt = 0; nt < NT; ++nt)                      \
@@ -308,7 +365,7 @@ __global__ __launch_bounds__(64 * KS) DG_NO_PK32 void decode_gemm_kernel(GemmArg
 
 // int4 keeps two fp32 tiles live per (nt, mt), the group sum and the
 // accumulator: 4 x 3 and 4 x 4 tiles do not fit the register file (they spill)
-// and are not instantiated
+// and are not instantiated.  MXFP4 keeps one and has every tile.
 template <typename W, int NT, int MT>
 constexpr bool gemm_tile_ok = !(W::GROUPED && NT * MT > 8);
 
@@ -343,7 +400,8 @@ bool gemm_launch(const GemmArgs<W>& a, int ks, int nt, int mt, hipStream_t s) {
 inline bool al16(const void* p) { return (uintptr_t)p % 16 == 0; }
 
 // Launch table, filled from the sweep in profiles/decode_rows/ (medians of three
-// per figure): per measured (N, K) and format {16-bit, int8, int4} the wave
+// per figure): per measured (N, K) and format {16-bit, int8, int4; MXFP4 takes
+// int4's column, its own sweep is not taken yet} the wave
 // count ks -- one per (N, K, format), it fixes the order of a row's sum; the
 // 16-bit column keeps gemv_kernel's rule, so that a row has the bits the GEMV
 // gives it and a speculative window step repeats the plain loop's logits -- and
@@ -382,12 +440,13 @@ const GemmRule GEMM_RULES[] = {
 // shape the launch table leaves to the vendor GEMM.
 template <typename W>
 int gemm_entry(int dt, int epi, int M, int N, int K, const void* x, long ldx, const void* w,
-               long ldw, const float* scale, const void* bias, const void* res, long ldres,
+               long ldw, const typename W::sc* scale, const void* bias, const void* res, long ldres,
                void* y, long ldy, void* kc, void* vc, const long* pos, const int* rows, int heads,
                int head_dim, int maxlen, int nt, int ks, hipStream_t s) {
   if (M < 17 || M > 64 || N < 1 || K < 1024 || K % 1024 != 0 || (ldx % 8) ||
       (ldw * sizeof(typename W::elt) % 16) || !al16(x) || !al16(w) || y == nullptr ||
-      ((W::SCALED || W::GROUPED) && scale == nullptr))
+      ((W::SCALED || W::GROUPED) && scale == nullptr) ||
+      (W::OPSCALED && (scale == nullptr || !al16(scale))))
     return 0;
   if (epi < GV_BIAS || epi > GV_QKV) return 0;
   if (epi == GV_RES && res == nullptr) return 0;
@@ -462,4 +521,13 @@ extern "C" int fx_decode_gemm_w4(int dt, int epi, int M, int N, int K, const voi
                                  int head_dim, int maxlen, int nt, int ks, hipStream_t s) {
   return gemm_entry<G4>(dt, epi, M, N, K, x, ldx, wq, ldw, wscale, bias, res, ldres, y, ldy, kc,
                         vc, pos, rows, heads, head_dim, maxlen, nt, ks, s);
+}
+
+extern "C" int fx_decode_gemm_mx4(int dt, int epi, int M, int N, int K, const void* x, long ldx,
+                                  const uint8_t* wq, long ldw, const uint8_t* wscale,
+                                  const void* bias, const void* res, long ldres, void* y, long ldy,
+                                  void* kc, void* vc, const long* pos, const int* rows, int heads,
+                                  int head_dim, int maxlen, int nt, int ks, hipStream_t s) {
+  return gemm_entry<GM4>(dt, epi, M, N, K, x, ldx, wq, ldw, wscale, bias, res, ldres, y, ldy, kc,
+                         vc, pos, rows, heads, head_dim, maxlen, nt, ks, s);
 }

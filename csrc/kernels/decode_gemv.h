@@ -4,7 +4,8 @@
 // kernel, the launch ladder and the host entry once; a weight format is a
 // small policy type W (decode_gemv.hip: 16-bit, decode_gemv_w8.hip: int8 with
 // a scale per output row, decode_gemv_w4.hip: int4 with a scale per k-group
-// and output row) that supplies
+// and output row, decode_gemv_mx4.hip: MXFP4 with an e8m0 scale per 32 k of a
+// row) that supplies
 //   elt, reg      weight element type and the 16-byte per-lane register type
 //   PACK          weights per elt (1; int4: 2 per byte)
 //   Ptrs          the weight pointer block of the argument struct: w (const
@@ -20,6 +21,13 @@
 //                 the lane's four scales of a chunk are loaded with the chunk's
 //                 weights and mma_batch takes them as a fourth argument (it
 //                 sums the chunk from zero and adds sum * scale to acc)
+//   OPSCALED      the scale belongs to the weight operand: Ptrs::scale is one
+//                 byte per (row, 32 k), stored so that one dword holds a lane's
+//                 four scales of a chunk pair (decode_gemv_mx4.hip).  The lane
+//                 that loads the weights loads that dword in the same batch,
+//                 and mma_batch takes it with the chunk's parity in the pair;
+//                 the conversion applies the scale, nothing is left for the
+//                 accumulator or the epilogue
 //   U, U_MIN      chunks per load batch: U, or U_MIN when a wave's K range is
 //                 no multiple of U chunks
 //   STEADY_LOOP   which of the kernel's two K-loop schedules runs
@@ -104,6 +112,32 @@ __device__ __forceinline__ short8 cvt8(uint32_t lo, uint32_t hi) {
   return __builtin_bit_cast(short8, o);
 }
 
+// MXFP4 weight operands (WMX4; GM4 of decode_gemm.hip)
+// an e8m0 scale byte (the low byte of v; 1..254) -> the fp32 2^(e - 127)
+__device__ __forceinline__ float mx4_scale(uint32_t v) {
+  return __builtin_bit_cast(float, (v & 0xFFu) << 23);
+}
+// eight e2m1 (one dword: byte j = elements 2j, 2j + 1 in its low, high nibble)
+// times scale -> one MFMA operand in element order: v_cvt_scalef32_pk_*_fp4,
+// one instruction per byte.  Exact: a code times a power of two is a 16-bit
+// float (fp16: while it is a normal one).
+template <typename T>
+__device__ __forceinline__ short8 mx4_cvt8(uint32_t v, float scale) {
+  uint4 o;
+  if constexpr (std::is_same<T, bf16>::value) {
+    o.x = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, scale, 0));
+    o.y = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, scale, 1));
+    o.z = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, scale, 2));
+    o.w = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, scale, 3));
+  } else {
+    o.x = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(v, scale, 0));
+    o.y = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(v, scale, 1));
+    o.z = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(v, scale, 2));
+    o.w = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(v, scale, 3));
+  }
+  return __builtin_bit_cast(short8, o);
+}
+
 template <typename W, int U>
 __device__ __forceinline__ void load_w(typename W::reg (&wv)[U][2], const typename W::elt* wp,
                                        int c) {
@@ -155,22 +189,43 @@ __device__ __forceinline__ void load_s(floatx4 (&sv)[U], const float* sp, int N,
   }
 }
 
+// OPSCALED: the scale dwords of the lane's row for chunks c .. c + U - 1 of the
+// wave's K range (ep: the row's scales at the range's first chunk pair and the
+// lane's group, c0: the range's first chunk).  One dword serves a chunk pair:
+// an even U starts every batch on an even chunk (the host gives U chunks per
+// batch only to a range of a multiple of U chunks) and loads once per pair.
+template <typename W, int U>
+__device__ __forceinline__ void load_e(uint32_t (&ev)[U], const uint8_t* ep, int c0, int c) {
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    if (U % 2 == 0 && (u & 1))
+      ev[u] = ev[u - 1];
+    else
+      ev[u] = *reinterpret_cast<const uint32_t*>(ep + (((c0 & 1) + c + u) >> 1) * 16);
+  }
+}
+
 // The kernel's load and MFMA steps; with W::GROUPED they carry the chunk scales
-// (sa / sb beside wa / wb).  Macros, not functions: a further level of inlining
-// around these calls moves the code generation of every instantiation.
-#define GV_LOAD_W(w, s, c)                                        \
+// (sa / sb beside wa / wb), with W::OPSCALED the operand scale dwords (ea / eb)
+// and the parity of the set's first chunk.  Macros, not functions: a further
+// level of inlining around these calls moves the code generation of every
+// instantiation.
+#define GV_LOAD_W(w, s, e, c)                                     \
   do {                                                            \
     load_w<W, U>(w, wp, c);                                       \
     if constexpr (W::GROUPED) load_s<W, U>(s, sp, a.N, nj, c);    \
+    if constexpr (W::OPSCALED) load_e<W, U>(e, ep, c0, c);        \
   } while (0)
-#define GV_LOAD_BATCH(XL, w, x, s, c)                             \
+#define GV_LOAD_BATCH(XL, w, x, s, e, c)                          \
   do {                                                            \
     load_batch<W, U, XL>(w, x, wp, xp, c);                        \
     if constexpr (W::GROUPED) load_s<W, U>(s, sp, a.N, nj, c);    \
+    if constexpr (W::OPSCALED) load_e<W, U>(e, ep, c0, c);        \
   } while (0)
-#define GV_MMA(w, x, s)                                           \
+#define GV_MMA(w, x, s, e, par)                                   \
   do {                                                            \
     if constexpr (W::GROUPED) W::template mma_batch<T, U>(acc, w, x, s); \
+    else if constexpr (W::OPSCALED) W::template mma_batch<T, U>(acc, w, x, e, par); \
     else W::template mma_batch<T, U>(acc, w, x);                  \
   } while (0)
 
@@ -316,6 +371,18 @@ __global__ __launch_bounds__(64 * GV_KS) void gemv_kernel(GemvArgs<W> a) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) nj[j] = min(n0 + (4 * g + j) % RW, a.N - 1);
   }
+  // OPSCALED: scale dwords of the two register sets, the lane's scale row at
+  // the chunk pair of this wave's first chunk c0, and the parity in its pair of
+  // each set's first chunk (set a holds chunks 0, 2U, .., set b chunks U, 3U, ..)
+  uint32_t ea[W::OPSCALED ? U : 1], eb[W::OPSCALED ? U : 1];
+  const uint8_t* ep = nullptr;
+  int c0 = 0, pa = 0, pb = 0;
+  if constexpr (W::OPSCALED) {
+    c0 = kb / W::CHUNK;
+    ep = a.wp.scale + (long)nrow * (a.K / 32) + (c0 >> 1) * 16 + 4 * g;
+    pa = c0 & 1;
+    pb = (c0 + U) & 1;
+  }
   if constexpr (W::STEADY_LOOP) {
     // Branch-free steady loop with peeled head and tail: no branch around the
     // loads, so the compiler counts vmcnt exactly and batch c+1 really stays in
@@ -324,55 +391,55 @@ __global__ __launch_bounds__(64 * GV_KS) void gemv_kernel(GemvArgs<W> a) {
     int c = 0;
     bool done = false;
     if constexpr (LN) {
-      GV_LOAD_W(wa, sa, 0);
-      if (U < nch) GV_LOAD_W(wb, sb, U);
+      GV_LOAD_W(wa, sa, ea, 0);
+      if (U < nch) GV_LOAD_W(wb, sb, eb, U);
       ln_prologue<W, T, 64 * GV_KS, LNR>(a, xs_dyn, red);
       load_x<W, U, true>(xa, xp, 0);
       if (U < nch) {
         load_x<W, U, true>(xb, xp, U);
-        GV_MMA(wa, xa, sa);
-        if (2 * U < nch) GV_LOAD_BATCH(LN, wa, xa, sa, 2 * U);
+        GV_MMA(wa, xa, sa, ea, pa);
+        if (2 * U < nch) GV_LOAD_BATCH(LN, wa, xa, sa, ea, 2 * U);
         else done = true;
-        GV_MMA(wb, xb, sb);
+        GV_MMA(wb, xb, sb, eb, pb);
         c = 2 * U;
       }
     } else {
-      GV_LOAD_BATCH(false, wa, xa, sa, 0);
+      GV_LOAD_BATCH(false, wa, xa, sa, ea, 0);
     }
     if (!done) {
       // set a holds batch c
       for (; c + 2 * U < nch; c += 2 * U) {
-        GV_LOAD_BATCH(LN, wb, xb, sb, c + U);
-        GV_MMA(wa, xa, sa);
-        GV_LOAD_BATCH(LN, wa, xa, sa, c + 2 * U);
-        GV_MMA(wb, xb, sb);
+        GV_LOAD_BATCH(LN, wb, xb, sb, eb, c + U);
+        GV_MMA(wa, xa, sa, ea, pa);
+        GV_LOAD_BATCH(LN, wa, xa, sa, ea, c + 2 * U);
+        GV_MMA(wb, xb, sb, eb, pb);
       }
       if (c + U < nch) {
-        GV_LOAD_BATCH(LN, wb, xb, sb, c + U);
-        GV_MMA(wa, xa, sa);
-        GV_MMA(wb, xb, sb);
+        GV_LOAD_BATCH(LN, wb, xb, sb, eb, c + U);
+        GV_MMA(wa, xa, sa, ea, pa);
+        GV_MMA(wb, xb, sb, eb, pb);
       } else {
-        GV_MMA(wa, xa, sa);
+        GV_MMA(wa, xa, sa, ea, pa);
       }
     }
   } else {
     // Guarded loop with break: every load sits behind a bounds test.
     if constexpr (LN) {
-      GV_LOAD_W(wa, sa, 0);
-      if (U < nch) GV_LOAD_W(wb, sb, U);
+      GV_LOAD_W(wa, sa, ea, 0);
+      if (U < nch) GV_LOAD_W(wb, sb, eb, U);
       ln_prologue<W, T, 64 * GV_KS, LNR>(a, xs_dyn, red);
       load_x<W, U, true>(xa, xp, 0);
       if (U < nch) load_x<W, U, true>(xb, xp, U);
     } else {
-      GV_LOAD_BATCH(false, wa, xa, sa, 0);
+      GV_LOAD_BATCH(false, wa, xa, sa, ea, 0);
     }
     for (int c = 0; c < nch; c += 2 * U) {
       if (!LN || c > 0)
-        if (c + U < nch) GV_LOAD_BATCH(LN, wb, xb, sb, c + U);
-      GV_MMA(wa, xa, sa);
+        if (c + U < nch) GV_LOAD_BATCH(LN, wb, xb, sb, eb, c + U);
+      GV_MMA(wa, xa, sa, ea, pa);
       if (c + U >= nch) break;
-      if (c + 2 * U < nch) GV_LOAD_BATCH(LN, wa, xa, sa, c + 2 * U);
-      GV_MMA(wb, xb, sb);
+      if (c + 2 * U < nch) GV_LOAD_BATCH(LN, wa, xa, sa, ea, c + 2 * U);
+      GV_MMA(wb, xb, sb, eb, pb);
     }
   }
   if constexpr (LN) __syncthreads();  // red[] doubled as the LN scratch

@@ -57,7 +57,7 @@ struct W4 {
     bool valid() const { return (uintptr_t)w % 16 == 0 && scale != nullptr; }
   };
   static constexpr int CHUNK = 256, PACK = 2;
-  static constexpr bool SCALED = false, GROUPED = true;
+  static constexpr bool SCALED = false, GROUPED = true, OPSCALED = false;
   static constexpr int U = 1, U_MIN = 1;
   static constexpr bool STEADY_LOOP = true;
   static constexpr const char* PIN_KS = "FLEETX_GEMV_W4_KS";

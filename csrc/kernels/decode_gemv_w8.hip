@@ -33,7 +33,7 @@ struct W8 {
     bool valid() const { return (uintptr_t)w % 16 == 0 && scale != nullptr; }
   };
   static constexpr int CHUNK = 128, PACK = 1;
-  static constexpr bool SCALED = true, GROUPED = false;
+  static constexpr bool SCALED = true, GROUPED = false, OPSCALED = false;
   static constexpr int U = 2, U_MIN = 1;
   static constexpr bool STEADY_LOOP = true;
   static constexpr const char* PIN_KS = "FLEETX_GEMV_W8_KS";

@@ -132,6 +132,11 @@ int fx_decode_gemv_w8(int, int, int, int, int, const void*, long, const int8_t*,
 int fx_decode_gemv_w4(int, int, int, int, int, const void*, long, const uint8_t*, long, const float*,
                       const void*, const void*, long, void*, long, void*, void*, const long*, const int*, int,
                       int, int, const void*, const void*, float, hipStream_t);
+// decode_gemv_mx4.hip: MXFP4 weights, e8m0 scale bytes [N, K / 32] in the kernel's block order
+int fx_decode_gemv_mx4(int, int, int, int, int, const void*, long, const uint8_t*, long,
+                       const uint8_t*, const void*, const void*, long, void*, long, void*, void*,
+                       const long*, const int*, int, int, int, const void*, const void*, float,
+                       hipStream_t);
 // decode_gemm.hip: the same for 17..64 rows, without the LayerNorm triple, with (nt, ks)
 int fx_decode_gemm(int, int, int, int, int, const void*, long, const void*, long, const void*,
                    const void*, long, void*, long, void*, void*, const long*, const int*, int, int, int,
@@ -142,6 +147,9 @@ int fx_decode_gemm_w8(int, int, int, int, int, const void*, long, const int8_t*,
 int fx_decode_gemm_w4(int, int, int, int, int, const void*, long, const uint8_t*, long, const float*,
                       const void*, const void*, long, void*, long, void*, void*, const long*, const int*, int,
                       int, int, int, int, hipStream_t);
+int fx_decode_gemm_mx4(int, int, int, int, int, const void*, long, const uint8_t*, long,
+                       const uint8_t*, const void*, const void*, long, void*, long, void*, void*,
+                       const long*, const int*, int, int, int, int, int, hipStream_t);
 hipStream_t fx_cumask_stream_create(int, int*);
 int fx_stream_destroy(hipStream_t);
 int fx_comm_max_world();

@@ -365,7 +365,8 @@ _LN_FUSE = os.environ.get("FLEETX_DECODE_LN_FUSE", "1") == "1"
 # size, the GEMV's twin for 17..64 rows); a quantised copy is stored as (GEMV
 # name, q, scale), so the format travels with it
 _WEIGHT_QUANT = {"int8": ("quantize_weight_int8", "decode_linear_w8", 1, "decode_gemm_w8"),
-                 "int4_g256": ("quantize_weight_int4", "decode_linear_w4", 256, "decode_gemm_w4")}
+                 "int4_g256": ("quantize_weight_int4", "decode_linear_w4", 256, "decode_gemm_w4"),
+                 "mxfp4": ("quantize_weight_mxfp4", "decode_linear_mx4", 32, "decode_gemm_mx4")}
 _ROWS_TWIN = {v[1]: v[3] for v in _WEIGHT_QUANT.values()}
 
 
@@ -827,7 +828,7 @@ class GPTForGeneration(torch.nn.Module):
             procs.append(ForcedEOSTokenLogitsProcessor(max_len, self.forced_eos_token_id))
         return procs
 
-    # ---- weight-only quantised decode (weight_quant: int8 / int4_g256)
+    # ---- weight-only quantised decode (weight_quant: int8 / int4_g256 / mxfp4)
     def _w8_sources(self):
         """The weights the decode step streams: four per fusable layer and the
         tied embedding table (as the LM head)."""

@@ -8,6 +8,8 @@ from .loss_embed import softmax_cross_entropy, embedding  # noqa: F401
 from .quant import fake_quant, quantize_weight_int8, dequantize_weight_int8  # noqa: F401
 from .quant import (quantize_weight_int4, dequantize_weight_int4, pack_int4,  # noqa: F401
                     unpack_int4)
+from .quant import (quantize_weight_mxfp4, dequantize_weight_mxfp4, pack_mxfp4,  # noqa: F401
+                    unpack_mxfp4)
 from .sampling import fused_sample, select_token, SelectState  # noqa: F401
 from .sampling import spec_verify, SpecState  # noqa: F401
 from .sampling import coupled_sample, coupled_keys  # noqa: F401

@@ -430,33 +430,44 @@ def wgrad_16(dy2, x2):
 # ----------------------------------------------------------------------------
 # decode-time skinny GEMM (csrc/kernels/decode_gemv.h: one kernel template over
 # the weight operand -- decode_gemv.hip 16-bit, decode_gemv_w8.hip int8,
-# decode_gemv_w4.hip int4 with a scale per group of 256 k)
+# decode_gemv_w4.hip int4 with a scale per group of 256 k, decode_gemv_mx4.hip
+# MXFP4 with an e8m0 scale per group of 32 k)
 # ----------------------------------------------------------------------------
 GV_BIAS, GV_GELU, GV_RES, GV_QKV = range(4)
 
+# quantised weight format -> (weight dtype, weights per element, scale dtype,
+# scale shape for (N, K) -- None: any shape of N elements --, kernel suffix)
+_WFMT = {"int8": (torch.int8, 1, torch.float32, lambda N, K: None, "_w8"),
+         "int4": (torch.uint8, 2, torch.float32, lambda N, K: (K // 256, N), "_w4"),
+         "mxfp4": (torch.uint8, 2, torch.uint8, lambda N, K: (N, K // 32), "_mx4")}
 
-def _decode_gemv(x, w, wscale, bias, epi, res, qkv_cache, ln, int4=False):
-    """The body of ``decode_linear`` (``wscale`` None: ``w`` is a 16-bit weight
-    of ``x.dtype``), ``decode_linear_w8`` (``w`` int8, ``wscale`` fp32 [N]) and
-    ``decode_linear_w4`` (``int4``: ``w`` packed uint8 [N, K / 2], ``wscale``
-    fp32 [K / 256, N]): the checks, the QKV unpacking, the output and the call.
-    None for a call the kernel does not cover; malformed caches / residual
-    assert."""
+
+def _wscale_ok(fmt, wscale, N, K):
+    sdtype, shape = _WFMT[fmt][2], _WFMT[fmt][3](N, K)
+    return (wscale.dtype == sdtype and wscale.is_cuda and wscale.is_contiguous()
+            and (wscale.numel() == N if shape is None else wscale.shape == shape))
+
+
+def _decode_gemv(x, w, wscale, bias, epi, res, qkv_cache, ln, fmt=None):
+    """The body of ``decode_linear`` (``fmt`` None: ``w`` is a 16-bit weight
+    of ``x.dtype``), ``decode_linear_w8`` (``"int8"``: ``w`` int8, ``wscale``
+    fp32 [N]), ``decode_linear_w4`` (``"int4"``: ``w`` packed uint8 [N, K / 2],
+    ``wscale`` fp32 [K / 256, N]) and ``decode_linear_mx4`` (``"mxfp4"``: ``w``
+    packed uint8 [N, K / 2], ``wscale`` uint8 [N, K / 32]): the checks, the QKV
+    unpacking, the output and the call.  None for a call the kernel does not
+    cover; malformed caches / residual assert."""
     if not x.is_cuda or x.dim() != 2 or x.shape[0] < 1 or x.shape[0] > 16 \
             or x.dtype not in (torch.bfloat16, torch.float16):
         return None
     M, K = x.shape
-    wdtype = x.dtype if wscale is None else torch.uint8 if int4 else torch.int8
-    if w.dim() != 2 or w.dtype != wdtype or not w.is_cuda or w.shape[1] * (2 if int4 else 1) != K:
+    wdtype, wpack = (x.dtype, 1) if fmt is None else _WFMT[fmt][:2]
+    if w.dim() != 2 or w.dtype != wdtype or not w.is_cuda or w.shape[1] * wpack != K:
         return None
     N = w.shape[0]
     if w.stride(1) != 1 or x.stride(1) != 1 or K % 1024 or x.stride(0) % 8 \
             or (w.stride(0) * w.element_size()) % 16 or w.data_ptr() % 16 or x.data_ptr() % 16:
         return None
-    if wscale is not None and (wscale.dtype != torch.float32 or not wscale.is_cuda
-                               or (wscale.shape != (K // 256, N) if int4
-                                   else wscale.numel() != N)
-                               or not wscale.is_contiguous()):
+    if fmt is not None and not _wscale_ok(fmt, wscale, N, K):
         return None
     if bias is not None and (bias.dtype != x.dtype or bias.numel() != N
                              or not bias.is_contiguous()):
@@ -495,12 +506,10 @@ def _decode_gemv(x, w, wscale, bias, epi, res, qkv_cache, ln, int4=False):
             _lib.ptr(kc), _lib.ptr(vc), _lib.ptr(pos), _lib.ptr(rows), heads, hd, maxlen,
             _lib.ptr(ln[0]) if ln is not None else 0, _lib.ptr(ln[1]) if ln is not None else 0,
             float(ln[2]) if ln is not None else 0.0, _lib.stream())
-    if wscale is None:
+    if fmt is None:
         nb = k.decode_gemv(*head, *tail)
-    elif int4:
-        nb = k.decode_gemv_w4(*head, wscale.data_ptr(), *tail)
     else:
-        nb = k.decode_gemv_w8(*head, wscale.data_ptr(), *tail)
+        nb = getattr(k, "decode_gemv" + _WFMT[fmt][4])(*head, wscale.data_ptr(), *tail)
     if nb == 0:
         return None
     _lib.maybe_sync()
@@ -538,7 +547,7 @@ def decode_linear_w8(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, qkv_cache=
     caller then uses the 16-bit weight)."""
     if wscale is None:
         return None
-    return _decode_gemv(x, wq, wscale, bias, epi, res, qkv_cache, ln)
+    return _decode_gemv(x, wq, wscale, bias, epi, res, qkv_cache, ln, fmt="int8")
 
 
 def decode_linear_w4(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, qkv_cache=None, ln=None):
@@ -553,33 +562,46 @@ def decode_linear_w4(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, qkv_cache=
     caller then uses the 16-bit weight)."""
     if wscale is None:
         return None
-    return _decode_gemv(x, wq, wscale, bias, epi, res, qkv_cache, ln, int4=True)
+    return _decode_gemv(x, wq, wscale, bias, epi, res, qkv_cache, ln, fmt="int4")
+
+
+def decode_linear_mx4(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, qkv_cache=None, ln=None):
+    """``decode_linear`` with a weight-only MXFP4 weight: ``wq`` packed uint8
+    [N, K / 2] (e2m1) and ``wscale`` uint8 [N, K / 32] (e8m0, one per group of
+    32 k) from ``ops.quantize_weight_mxfp4``.  The hardware conversion
+    (``v_cvt_scalef32_pk_*_fp4``) turns eight weights and their group scale
+    into an MFMA operand of ``x.dtype`` exactly -- for fp16 while ``2^-13 <=
+    scale <= 2^13`` --, the products accumulate in fp32; the bias and the
+    epilogue follow as in ``decode_linear``.
+
+    Returns the output, or None when the kernel does not cover the call (the
+    caller then uses the 16-bit weight)."""
+    if wscale is None:
+        return None
+    return _decode_gemv(x, wq, wscale, bias, epi, res, qkv_cache, ln, fmt="mxfp4")
 
 
 # ----------------------------------------------------------------------------
 # the same for 17..64 rows (csrc/kernels/decode_gemm.hip: a register-tiled
 # skinny GEMM over the same weight stream, same weight formats and epilogues)
 # ----------------------------------------------------------------------------
-def _decode_gemm(x, w, wscale, bias, epi, res, qkv_cache, shape, int4=False):
-    """The body of ``decode_gemm`` / ``decode_gemm_w8`` / ``decode_gemm_w4``,
-    after ``_decode_gemv``: the checks, the QKV unpacking, the output and the
+def _decode_gemm(x, w, wscale, bias, epi, res, qkv_cache, shape, fmt=None):
+    """The body of ``decode_gemm`` / ``decode_gemm_w8`` / ``decode_gemm_w4`` /
+    ``decode_gemm_mx4``, after ``_decode_gemv``: the checks, the QKV unpacking, the output and the
     call.  None for a call the kernel does not cover; malformed caches /
     residual assert."""
     if not x.is_cuda or x.dim() != 2 or x.shape[0] < 17 or x.shape[0] > 64 \
             or x.dtype not in (torch.bfloat16, torch.float16):
         return None
     M, K = x.shape
-    wdtype = x.dtype if wscale is None else torch.uint8 if int4 else torch.int8
-    if w.dim() != 2 or w.dtype != wdtype or not w.is_cuda or w.shape[1] * (2 if int4 else 1) != K:
+    wdtype, wpack = (x.dtype, 1) if fmt is None else _WFMT[fmt][:2]
+    if w.dim() != 2 or w.dtype != wdtype or not w.is_cuda or w.shape[1] * wpack != K:
         return None
     N = w.shape[0]
     if w.stride(1) != 1 or x.stride(1) != 1 or K % 1024 or x.stride(0) % 8 \
             or (w.stride(0) * w.element_size()) % 16 or w.data_ptr() % 16 or x.data_ptr() % 16:
         return None
-    if wscale is not None and (wscale.dtype != torch.float32 or not wscale.is_cuda
-                               or (wscale.shape != (K // 256, N) if int4
-                                   else wscale.numel() != N)
-                               or not wscale.is_contiguous()):
+    if fmt is not None and not _wscale_ok(fmt, wscale, N, K):
         return None
     if bias is not None and (bias.dtype != x.dtype or bias.numel() != N
                              or not bias.is_contiguous()):
@@ -613,12 +635,10 @@ def _decode_gemm(x, w, wscale, bias, epi, res, qkv_cache, shape, int4=False):
             res.stride(0) if epi == GV_RES else 0, y.data_ptr(), y.stride(0),
             _lib.ptr(kc), _lib.ptr(vc), _lib.ptr(pos), _lib.ptr(rows), heads, hd, maxlen,
             int(nt), int(ks), _lib.stream())
-    if wscale is None:
+    if fmt is None:
         nb = k.decode_gemm(*head, *tail)
-    elif int4:
-        nb = k.decode_gemm_w4(*head, wscale.data_ptr(), *tail)
     else:
-        nb = k.decode_gemm_w8(*head, wscale.data_ptr(), *tail)
+        nb = getattr(k, "decode_gemm" + _WFMT[fmt][4])(*head, wscale.data_ptr(), *tail)
     if nb == 0:
         return None
     _lib.maybe_sync()
@@ -645,7 +665,7 @@ def decode_gemm_w8(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, qkv_cache=No
     """``decode_gemm`` with the weight-only int8 weight of ``decode_linear_w8``."""
     if wscale is None:
         return None
-    return _decode_gemm(x, wq, wscale, bias, epi, res, qkv_cache, shape)
+    return _decode_gemm(x, wq, wscale, bias, epi, res, qkv_cache, shape, fmt="int8")
 
 
 def decode_gemm_w4(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, qkv_cache=None, shape=None):
@@ -653,4 +673,12 @@ def decode_gemm_w4(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, qkv_cache=No
     ``decode_linear_w4``."""
     if wscale is None:
         return None
-    return _decode_gemm(x, wq, wscale, bias, epi, res, qkv_cache, shape, int4=True)
+    return _decode_gemm(x, wq, wscale, bias, epi, res, qkv_cache, shape, fmt="int4")
+
+
+def decode_gemm_mx4(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, qkv_cache=None, shape=None):
+    """``decode_gemm`` with the weight-only MXFP4 weight of ``decode_linear_mx4``;
+    every tile shape up to ``nt = 4`` at 64 rows."""
+    if wscale is None:
+        return None
+    return _decode_gemm(x, wq, wscale, bias, epi, res, qkv_cache, shape, fmt="mxfp4")

@@ -7,7 +7,9 @@ Reference P11 / K23: paddleslim QAT with ``abs_max`` weight quantisation and
 Also the per-row weight-only int8 quantiser whose output the decode GEMV
 consumes (``quantize_weight_int8`` / ``ops.gemm.decode_linear_w8``), and the
 int4 quantiser with one scale per k-group of 256 (``quantize_weight_int4`` /
-``ops.gemm.decode_linear_w4``).
+``ops.gemm.decode_linear_w4``), and the MXFP4 quantiser (e2m1 elements, one
+power-of-two scale per 32 k; ``quantize_weight_mxfp4`` /
+``ops.gemm.decode_linear_mx4``).
 """
 import torch
 
@@ -128,3 +130,102 @@ def dequantize_weight_int4(packed, scale, dtype=torch.float32):
     n, k = q.shape
     wf = q.view(n, k // INT4_GROUP, INT4_GROUP).float() * scale.float().t()[:, :, None]
     return wf.view(n, k).to(dtype)
+
+
+# ----------------------------------------------------------------------------
+# weight-only MXFP4 (OCP microscaling: e2m1 elements, groups of 32 k, one e8m0
+# scale per group; consumed by ops.gemm.decode_linear_mx4)
+# ----------------------------------------------------------------------------
+MXFP4_GROUP = 32
+# the value of code c (bit 3: sign, bits 2..0: e2m1 magnitude)
+_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+_MX_BLOCK = 16  # scale bytes per storage block: 512 k, two of the kernel's 256-k chunks
+
+
+def _mx_scale_order(groups):
+    """Stored position -> group index of a row's scale bytes.  Whole blocks of
+    16 groups (512 k) are ordered [lane group g of 4][chunk c of 2][half j of
+    2] = group ``8 c + 2 g + j`` of the block, so the dword at byte ``4 g`` of
+    a block holds what the kernel lane that streams k ``64 g .. 64 g + 63`` of
+    either 256-k chunk needs; groups past the last whole block keep their
+    order (the kernels take K % 1024 == 0 only)."""
+    idx = torch.arange(groups)
+    full = groups // _MX_BLOCK * _MX_BLOCK
+    g, c, j = torch.meshgrid(torch.arange(4), torch.arange(2), torch.arange(2), indexing="ij")
+    blk = (8 * c + 2 * g + j).reshape(-1)
+    idx[:full] = (torch.arange(0, full, _MX_BLOCK)[:, None] + blk[None, :]).reshape(-1)
+    return idx
+
+
+def pack_mxfp4(codes, exps):
+    """Store uint8 e2m1 ``codes [N, K]`` (values 0..15, K % 32 == 0) and their
+    biased group exponents ``exps`` uint8 ``[N, K / 32]`` as the kernels read
+    them: ``(packed uint8 [N, K / 2], scale uint8 [N, K / 32])``.
+
+    Layout (shared only with ``unpack_mxfp4``, csrc/kernels/decode_gemv_mx4.hip
+    and GM4 of decode_gemm.hip): byte ``i`` of a packed row holds code ``2i``
+    in its low nibble and code ``2i + 1`` in its high nibble, the order in
+    which ``v_cvt_scalef32_pk_*_fp4`` unpacks a byte; the scale bytes of a row
+    are permuted by ``_mx_scale_order``."""
+    assert codes.dim() == 2 and codes.dtype == torch.uint8 and codes.shape[1] % MXFP4_GROUP == 0
+    n, k = codes.shape
+    assert exps.shape == (n, k // MXFP4_GROUP) and exps.dtype == torch.uint8
+    c = codes.view(n, k // 2, 2)
+    packed = (c[:, :, 0] | (c[:, :, 1] << 4)).contiguous()
+    order = _mx_scale_order(k // MXFP4_GROUP).to(exps.device)
+    return packed, exps[:, order].contiguous()
+
+
+def unpack_mxfp4(packed, scale):
+    """The exact inverse of ``pack_mxfp4``: ``(codes uint8 [N, K], exps uint8
+    [N, K / 32])``."""
+    assert packed.dim() == 2 and packed.dtype == torch.uint8 and scale.dtype == torch.uint8
+    n, kb = packed.shape
+    assert scale.shape == (n, kb * 2 // MXFP4_GROUP)
+    codes = torch.stack((packed & 0xF, packed >> 4), dim=2).reshape(n, kb * 2).contiguous()
+    exps = torch.empty_like(scale)
+    exps[:, _mx_scale_order(scale.shape[1]).to(scale.device)] = scale
+    return codes, exps
+
+
+def quantize_weight_mxfp4(w):
+    """MXFP4 quantisation of ``w [N, K]`` (K % 32 == 0, else ValueError).  Per
+    (row, group of 32 k) the scale is ``X = 2^e``, the smallest power of two
+    with ``amax <= 6 X``, so no element saturates; stored as the e8m0 byte
+    ``e + 127`` clamped to [1, 254] (127 for an all-zero group).  This rounds
+    the scale up where the OCP specification's conversion rounds it down
+    (``2^(floor(log2 amax) - 2)``, which saturates elements above ``6 X``);
+    the stored format is the same.  Elements are ``w / X`` rounded to nearest,
+    ties to even, onto the e2m1 values +-{0, 0.5, 1, 1.5, 2, 3, 4, 6}.
+
+    Returns ``(packed uint8 [N, K / 2], scale uint8 [N, K / 32])`` in the
+    layout of ``pack_mxfp4``.  fp16 models: the kernels convert exactly while
+    every ``code * X`` is a normal fp16, ``2^-13 <= X <= 2^13``; scales
+    outside that range are not covered there (bf16 holds them all).  Plain
+    torch ops: it runs once per weight."""
+    assert w.dim() == 2 and w.is_floating_point()
+    n, k = w.shape
+    if k % MXFP4_GROUP:
+        raise ValueError("quantize_weight_mxfp4: K = %d is no multiple of the group size %d"
+                         % (k, MXFP4_GROUP))
+    wf = w.detach().float().view(n, k // MXFP4_GROUP, MXFP4_GROUP)
+    amax = wf.abs().amax(dim=2)
+    # amax = m 2^ex, m in [0.5, 1): 6 * 2^(ex - 3) = 0.75 * 2^ex covers m <= 0.75
+    m, ex = torch.frexp(amax)
+    e = torch.where(m <= 0.75, ex - 3, ex - 2)
+    e = torch.where(amax > 0, e, torch.zeros_like(e)).clamp(-126, 127)
+    v = torch.ldexp(wf.abs(), -e[:, :, None])
+    mag = torch.where(v < 2, torch.round(v * 2),
+                      torch.where(v < 4, torch.round(v) + 2, torch.round(v / 2) + 4)).clamp(max=7)
+    codes = mag.to(torch.uint8) | (((wf < 0) & (mag > 0)).to(torch.uint8) << 3)
+    return pack_mxfp4(codes.view(n, k), (e + 127).to(torch.uint8))
+
+
+def dequantize_weight_mxfp4(packed, scale, dtype=torch.float32):
+    """``value(code) * 2^(e - 127)`` of each element's group: exact in fp32
+    and bf16, rounded once to ``dtype`` otherwise; ``[N, K]``."""
+    codes, exps = unpack_mxfp4(packed, scale)
+    n, k = codes.shape
+    lut = torch.tensor(_E2M1 + tuple(-x for x in _E2M1), device=codes.device)
+    val = lut[codes.long()].view(n, k // MXFP4_GROUP, MXFP4_GROUP)
+    return torch.ldexp(val, exps.int()[:, :, None] - 127).view(n, k).to(dtype)

@@ -5,6 +5,7 @@ hipBLASLt (F.linear) on the same operands.
     python tools/bench_gemv.py [--m 1 8 16]
     python tools/bench_gemv.py --w8 [--m 1 4 16] [--repeat 2]
     python tools/bench_gemv.py --w4 [--m 1 4 16] [--repeat 2]
+    python tools/bench_gemv.py --mx4 [--m 1 4 16 32 64] [--repeat 3]
     python tools/bench_gemv.py --rows 17 32 48 64 [--shape nt,ks | --sweep]
 
 ``--w8`` times the weight-only int8 GEMV (csrc/kernels/decode_gemv_w8.hip)
@@ -12,6 +13,9 @@ against the 16-bit one, alternating in one process on weights streamed from
 HBM (each series replayed from a HIP graph, so the figure is GPU time); ``--repeat`` runs each series that many times.
 ``--w4`` does the same for the int4 GEMV with group scales
 (csrc/kernels/decode_gemv_w4.hip); its records carry ``gemv_w4_us``.
+``--mx4`` times the MXFP4 kernels (csrc/kernels/decode_gemv_mx4.hip; above 16
+rows GM4 of decode_gemm.hip) against the int4 ones on copies of the same
+weights, the two series alternating; its records carry ``w4_us`` / ``mx4_us``.
 ``--rows`` times the skinny GEMM of 17..64 rows (csrc/kernels/decode_gemm.hip)
 in its three formats against the chain it replaces (the vendor GEMM with bias
 and the layer's separate GeLU / residual launch), the same way; ``--shape``
@@ -96,6 +100,40 @@ def main_w8(args, G):
         torch.cuda.empty_cache()
 
 
+def main_mx4(args, G):
+    """int4 (g256) against MXFP4 weights, GEMV (M <= 16) or skinny GEMM."""
+    from fleetx_amd import ops
+    for name in args.shapes or SHAPES:
+        N, K = SHAPES[name]
+        ncopy = max(2, -(-(1 << 31) // (N * K * 2)))   # >= 512 MiB of 4-bit weights
+        q4, qm = [], []
+        for _ in range(ncopy):
+            w = (torch.randn(N, K, device="cuda") * K ** -0.5).bfloat16()
+            q4.append(ops.quantize_weight_int4(w))
+            qm.append(ops.quantize_weight_mxfp4(w))
+        del w
+        b = torch.randn(N, device="cuda").bfloat16()
+        for M in args.m:
+            x = torch.randn(M, K, device="cuda").bfloat16()
+            f4, fm = (G.decode_linear_w4, G.decode_linear_mx4) if M <= 16 \
+                else (G.decode_gemm_w4, G.decode_gemm_mx4)
+            assert f4(x, *q4[0], b) is not None and fm(x, *qm[0], b) is not None
+            us4, usm = [], []
+            for _ in range(args.repeat):
+                us4.append(time_graph(lambda i: f4(x, *q4[i], b), ncopy))
+                usm.append(time_graph(lambda i: fm(x, *qm[i], b), ncopy))
+            med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+            print(json.dumps({"shape": name, "M": M, "N": N, "K": K,
+                              "w4_us": [round(u, 2) for u in us4],
+                              "mx4_us": [round(u, 2) for u in usm],
+                              "mx4_TB_s": round(N * K * 0.53125 / med(usm) / 1e6, 2),
+                              "speedup": round(med(us4) / med(usm), 3),
+                              "spread_w4_pct": round(100 * (max(us4) - min(us4)) / min(us4), 2)}),
+                  flush=True)
+        del q4, qm
+        torch.cuda.empty_cache()
+
+
 def main_rows(args, G):
     """The skinny GEMM at ``--rows`` against the unfused chain of the same call."""
     from fleetx_amd import ops
@@ -147,7 +185,9 @@ def main():
                     help="also time a weight resident in the Infinity Cache")
     ap.add_argument("--w8", action="store_true", help="16-bit vs weight-only int8 GEMV")
     ap.add_argument("--w4", action="store_true", help="16-bit vs weight-only int4 (g256) GEMV")
-    ap.add_argument("--repeat", type=int, default=2, help="--w8 / --w4: runs of each series")
+    ap.add_argument("--mx4", action="store_true", help="int4 (g256) vs MXFP4 GEMV / skinny GEMM")
+    ap.add_argument("--repeat", type=int, default=2,
+                    help="--w8 / --w4 / --mx4: runs of each series")
     ap.add_argument("--shapes", nargs="+", default=None, choices=sorted(SHAPES))
     ap.add_argument("--rows", type=int, nargs="+", default=None,
                     help="time the 17..64-row skinny GEMM at these row counts")
@@ -157,6 +197,8 @@ def main():
     from fleetx_amd.ops import gemm as G
     if args.rows:
         return main_rows(args, G)
+    if args.mx4:
+        return main_mx4(args, G)
     if args.w8 or args.w4:
         return main_w8(args, G)
     for name, (N, K) in SHAPES.items():

@@ -4,7 +4,7 @@ epilogues).  Random-init weights, bf16.
 
     python tools/bench_generation.py [--model gpt3-1.3B] [--batch 1 8 16] [--tokens 64]
                                      [--strategy beam_search --num-beams 4]
-                                     [--weight-quant int8 int4_g256 [--repeat 2]]
+                                     [--weight-quant int8 int4_g256 mxfp4 [--repeat 2]]
                                      [--device-loop [--repeat 3]]
                                      [--spec-draft int4_g256 --spec-tokens 2 4
                                       [--spec-device-loop]]
@@ -49,11 +49,11 @@ def main():
     ap.add_argument("--strategy", default="greedy_search",
                     choices=["greedy_search", "sampling", "beam_search"])
     ap.add_argument("--num-beams", type=int, default=1)
-    ap.add_argument("--weight-quant", default=[], nargs="+", choices=["int8", "int4_g256"],
+    ap.add_argument("--weight-quant", default=[], nargs="+", choices=["int8", "int4_g256", "mxfp4"],
                     help="also run the fused decode on weight-only int8 / int4 copies")
     ap.add_argument("--device-loop", action="store_true",
                     help="also run every fused series with Generation.device_loop")
-    ap.add_argument("--spec-draft", default=None, choices=["int8", "int4_g256"],
+    ap.add_argument("--spec-draft", default=None, choices=["int8", "int4_g256", "mxfp4"],
                     help="also run speculative greedy decoding with this draft format")
     ap.add_argument("--spec-tokens", type=int, nargs="+", default=[4])
     ap.add_argument("--sampler", default="inverse_cdf", choices=["inverse_cdf", "coupled"],
