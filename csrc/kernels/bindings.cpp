@@ -407,6 +407,29 @@ PYBIND11_MODULE(_kernels, m) {
                               P(y), ldy, P(kc), P(vc), reinterpret_cast<const long*>(pos),
                               reinterpret_cast<const int*>(rows), heads, head_dim, maxlen, nt, ks, S(st));
   });
+  // quantised prefill GEMM for 65 rows and more (prefill_gemm.hip): no QKV scatter, launch
+  // shape (mt, nt; 0 0: the library's rule)
+  m.def("prefill_gemm_w8", [](int dt, int epi, int M, int N, int K, ptr x, long ldx, ptr wq,
+                              long ldw, ptr wscale, ptr bias, ptr res, long ldres, ptr y, long ldy,
+                              int mt, int nt, ptr st) {
+    return fx_prefill_gemm_w8(dt, epi, M, N, K, CP(x), ldx, reinterpret_cast<const int8_t*>(wq),
+                              ldw, reinterpret_cast<const float*>(wscale), CP(bias), CP(res), ldres,
+                              P(y), ldy, mt, nt, S(st));
+  });
+  m.def("prefill_gemm_w4", [](int dt, int epi, int M, int N, int K, ptr x, long ldx, ptr wq,
+                              long ldw, ptr wscale, ptr bias, ptr res, long ldres, ptr y, long ldy,
+                              int mt, int nt, ptr st) {
+    return fx_prefill_gemm_w4(dt, epi, M, N, K, CP(x), ldx, reinterpret_cast<const uint8_t*>(wq),
+                              ldw, reinterpret_cast<const float*>(wscale), CP(bias), CP(res), ldres,
+                              P(y), ldy, mt, nt, S(st));
+  });
+  m.def("prefill_gemm_mx4", [](int dt, int epi, int M, int N, int K, ptr x, long ldx, ptr wq,
+                               long ldw, ptr wscale, ptr bias, ptr res, long ldres, ptr y, long ldy,
+                               int mt, int nt, ptr st) {
+    return fx_prefill_gemm_mx4(dt, epi, M, N, K, CP(x), ldx, reinterpret_cast<const uint8_t*>(wq),
+                               ldw, reinterpret_cast<const uint8_t*>(wscale), CP(bias), CP(res),
+                               ldres, P(y), ldy, mt, nt, S(st));
+  });
   // CU-masked stream (streams.hip): returns (stream handle, CUs selected)
   m.def("cumask_stream_create", [](int ncu) {
     int got = 0;

@@ -150,6 +150,17 @@ int fx_decode_gemm_w4(int, int, int, int, int, const void*, long, const uint8_t*
 int fx_decode_gemm_mx4(int, int, int, int, int, const void*, long, const uint8_t*, long,
                        const uint8_t*, const void*, const void*, long, void*, long, void*, void*,
                        const long*, const int*, int, int, int, int, int, hipStream_t);
+// prefill_gemm.hip: the same packed copies at 65 rows and more; GV_BIAS / GV_GELU / GV_RES,
+// launch shape (mt, nt), 0 0: the library's rule
+int fx_prefill_gemm_w8(int, int, int, int, int, const void*, long, const int8_t*, long,
+                       const float*, const void*, const void*, long, void*, long, int, int,
+                       hipStream_t);
+int fx_prefill_gemm_w4(int, int, int, int, int, const void*, long, const uint8_t*, long,
+                       const float*, const void*, const void*, long, void*, long, int, int,
+                       hipStream_t);
+int fx_prefill_gemm_mx4(int, int, int, int, int, const void*, long, const uint8_t*, long,
+                        const uint8_t*, const void*, const void*, long, void*, long, int, int,
+                        hipStream_t);
 hipStream_t fx_cumask_stream_create(int, int*);
 int fx_stream_destroy(hipStream_t);
 int fx_comm_max_world();

@@ -232,33 +232,38 @@ def _attend(cache, li, q, lens_after):
     return ops.decode_attention(q, cache.k[li], cache.v[li], lens_after)
 
 
-def _layer_prefill(layer, x, cache, li, lens):
-    """Full-prompt pass of one decoder layer that also fills the KV cache."""
+def _layer_prefill(layer, x, cache, li, lens, w8=None):
+    """Full-prompt pass of one decoder layer that also fills the KV cache.
+    ``w8`` (``weight_quant_prefill``): this layer's quantised copies; its four
+    linears then run on them (``_qkv_quant``, ``_layer_tail_quant``)."""
     attn = layer.attn
     h = layer.ln1(x)
-    qkv = attn.qkv_proj(h)
+    qkv = attn.qkv_proj(h) if w8 is None else _qkv_quant(layer, h, w8)
     b, s = qkv.shape[0], qkv.shape[1]
     qkv5 = qkv.view(b, s, attn.heads, 3, attn.head_dim)
     cache.k[li][:, :s] = qkv5[:, :, :, 1]
     cache.v[li][:, :s] = qkv5[:, :, :, 2]
     o = ops.flash_attention(qkv5[:, :, :, 0], qkv5[:, :, :, 1], qkv5[:, :, :, 2], causal=True,
                             kv_lens=lens).reshape(b, s, -1)
+    if w8 is not None:
+        return _layer_tail_quant(layer, x, o, w8)
     a, ab = attn.out_proj(o)
     x2, h2 = ops.add_layer_norm(a, ab, x, layer.ln2.weight, layer.ln2.bias, layer.ln2.eps)
     m, mb = layer.mlp(h2)
     return ops.bias_dropout_add(m, mb, x2)
 
 
-def _layer_prefill_at(layer, x, cache, li, q_starts, kv_lens, rows, keep):
+def _layer_prefill_at(layer, x, cache, li, q_starts, kv_lens, rows, keep, w8=None):
     """A block of new tokens per sample over a cache that holds their
     predecessors (a prefill chunk, a session turn): x [B, n, h]; token ``i`` of
     row ``b`` sits at position ``q_starts[b] + i`` and its K/V go to cache row
     ``rows[b, i]`` (the same number); ``kv_lens`` [B] keys are valid once the
     block is in.  ``keep``: None, or the (batch, token) index pair of the
-    tokens whose cache row exists (padding tokens past the cache are dropped)."""
+    tokens whose cache row exists (padding tokens past the cache are dropped).
+    ``w8``: as in ``_layer_prefill``."""
     attn = layer.attn
     h = layer.ln1(x)
-    qkv = attn.qkv_proj(h)
+    qkv = attn.qkv_proj(h) if w8 is None else _qkv_quant(layer, h, w8)
     b, s = qkv.shape[0], qkv.shape[1]
     qkv5 = qkv.view(b, s, attn.heads, 3, attn.head_dim)
     kc, vc = cache.k[li], cache.v[li]
@@ -271,6 +276,8 @@ def _layer_prefill_at(layer, x, cache, li, q_starts, kv_lens, rows, keep):
         kc[bi, rows[bi, si]] = qkv5[bi, si, :, 1]
         vc[bi, rows[bi, si]] = qkv5[bi, si, :, 2]
     o = ops.prefill_attention(qkv5[:, :, :, 0], kc, vc, q_starts, kv_lens).reshape(b, s, -1)
+    if w8 is not None:
+        return _layer_tail_quant(layer, x, o, w8)
     a, ab = attn.out_proj(o)
     x2, h2 = ops.add_layer_norm(a, ab, x, layer.ln2.weight, layer.ln2.bias, layer.ln2.eps)
     m, mb = layer.mlp(h2)
@@ -362,12 +369,16 @@ _LN_FUSE = os.environ.get("FLEETX_DECODE_LN_FUSE", "1") == "1"
 
 
 # weight_quant value -> (quantiser in ops, its decode GEMV in ops.gemm, k-group
-# size, the GEMV's twin for 17..64 rows); a quantised copy is stored as (GEMV
-# name, q, scale), so the format travels with it
-_WEIGHT_QUANT = {"int8": ("quantize_weight_int8", "decode_linear_w8", 1, "decode_gemm_w8"),
-                 "int4_g256": ("quantize_weight_int4", "decode_linear_w4", 256, "decode_gemm_w4"),
-                 "mxfp4": ("quantize_weight_mxfp4", "decode_linear_mx4", 32, "decode_gemm_mx4")}
+# size, the GEMV's twin for 17..64 rows, its twin above 64 rows); a quantised
+# copy is stored as (GEMV name, q, scale), so the format travels with it
+_WEIGHT_QUANT = {"int8": ("quantize_weight_int8", "decode_linear_w8", 1, "decode_gemm_w8",
+                          "prefill_gemm_w8"),
+                 "int4_g256": ("quantize_weight_int4", "decode_linear_w4", 256, "decode_gemm_w4",
+                               "prefill_gemm_w4"),
+                 "mxfp4": ("quantize_weight_mxfp4", "decode_linear_mx4", 32, "decode_gemm_mx4",
+                           "prefill_gemm_mx4")}
 _ROWS_TWIN = {v[1]: v[3] for v in _WEIGHT_QUANT.values()}
+_PREFILL_TWIN = {v[1]: v[4] for v in _WEIGHT_QUANT.values()}
 
 
 def _qlin(G, x, q8, *args, **kw):
@@ -409,6 +420,45 @@ def _dlin(G, x, lin, epi, q8, **kw):
         y = G.decode_gemm(x, lin.weight, lin.bias, epi, **kw)
         return y if y is not None else _ulin(G, x, lin, epi, **kw)
     return G.decode_linear(x, lin.weight, lin.bias, epi, **kw)
+
+
+def _plin(G, x, lin, epi, q8, res=None):
+    """One linear of the quantised prefill (``weight_quant_prefill``) on ``x``
+    [rows, K]: on the quantised copy ``q8``, by row count on the prefill GEMM
+    (above 64 rows), the skinny GEMM (17..64) or the decode GEMV (a one-row
+    session turn is valid), so the weights do not depend on the row count.  A
+    linear without a copy, or a call the kernel does not cover, runs that one
+    call on its 16-bit weight as ``_ulin`` does.  ``lin`` None: the LM head,
+    which has no bias and no fallback here (the result may be None)."""
+    x = x.contiguous()
+    if q8 is not None:
+        n = x.shape[0]
+        name = q8[0] if n <= 16 else _ROWS_TWIN[q8[0]] if n <= 64 else _PREFILL_TWIN[q8[0]]
+        y = getattr(G, name)(x, q8[1], q8[2], lin.bias if lin is not None else None, epi, res=res)
+        if y is not None or lin is None:
+            return y
+    return _ulin(G, x, lin, epi, res=res) if lin is not None else None
+
+
+def _qkv_quant(layer, h, w8):
+    """The packed QKV [B, S, 3 hidden] of the normalised ``h`` [B, S, hidden]
+    on the quantised copy; the caller writes K / V and attends as ever."""
+    from ....ops import gemm as G
+    b, s = h.shape[0], h.shape[1]
+    return _plin(G, h.reshape(b * s, -1), layer.attn.qkv_proj, G.GV_BIAS,
+                 w8.get("qkv_proj")).view(b, s, -1)
+
+
+def _layer_tail_quant(layer, x, o, w8):
+    """The rest of a prefill layer after the attention output ``o`` on the
+    quantised copies: [out-proj + bias + residual] -> LN2 -> [FFN1 + bias +
+    GeLU] -> [FFN2 + bias + residual], each one launch."""
+    from ....ops import gemm as G
+    b, s, hid = x.shape
+    x2d = x.reshape(b * s, hid)
+    x2 = _plin(G, o.reshape(b * s, -1), layer.attn.out_proj, G.GV_RES, w8.get("out_proj"), res=x2d)
+    f = _plin(G, layer.ln2(x2), layer.mlp.fc1, G.GV_GELU, w8.get("fc1"))
+    return _plin(G, f, layer.mlp.fc2, G.GV_RES, w8.get("fc2"), res=x2).view(b, s, hid)
 
 
 def _layer_decode_fused(layer, x, cache, li, pos, lens_after, w8=None, rows=None):
@@ -729,6 +779,14 @@ class GPTForGeneration(torch.nn.Module):
         if self.weight_quant is not None and self.weight_quant not in _WEIGHT_QUANT:
             raise ValueError("weight_quant must be None, %s (got %r)"
                              % (" or ".join(repr(k) for k in _WEIGHT_QUANT), self.weight_quant))
+        # the prefill (one pass, chunks, session turns) on the same quantised copies
+        self.weight_quant_prefill = c.get("weight_quant_prefill", False)
+        if not isinstance(self.weight_quant_prefill, bool):
+            raise ValueError("weight_quant_prefill must be true or false (got %r)"
+                             % (self.weight_quant_prefill,))
+        if self.weight_quant_prefill and self.weight_quant is None:
+            raise ValueError("weight_quant_prefill needs weight_quant: there are no quantised "
+                             "copies to prefill on")
         self._w8 = None        # {"layers": [{name: (GEMV name, q, scale)}], "head": (...)}
         self._w8_src = []      # (weight, _version, data_ptr) of every quantised weight
         self._w8_warned = False
@@ -844,7 +902,11 @@ class GPTForGeneration(torch.nn.Module):
         """(Re)build the quantised copies from the current 16-bit weights: the
         target's (``weight_quant``) and the draft's (``spec_draft``).  The
         16-bit weights stay resident (prefill and the embedding lookup use
-        them): the quantised path buys decode bandwidth, not memory.  Returns
+        them): the quantised path buys decode bandwidth, not memory.  With
+        ``weight_quant_prefill`` the prefill reads the quantised copies too;
+        what then still holds the 16-bit weights resident is the embedding
+        lookup (the tied table) and the linears that fall back (no copy, a
+        layer that is not fusable, a call a kernel does not cover).  Returns
         True when the quantised path is active; on CPU or under tensor parallel
         the keys are accepted and ignored with one warning (those paths do not
         stream weights through the decode GEMV).  A weight the format cannot
@@ -937,14 +999,20 @@ class GPTForGeneration(torch.nn.Module):
         x = self.gpt.final_ln(x)
         return self._logits(x[:, 0], q8["head"] if q8 is not None else None)
 
-    def _logits(self, h, q8=None):
+    def _logits(self, h, q8=None, any_rows=False):
         """``q8``: the quantised copy of the tied table (decode steps; the prefill's
-        last-token logits use the 16-bit table like the rest of the prefill)."""
+        last-token logits use the 16-bit table like the rest of the prefill,
+        unless ``weight_quant_prefill`` passes the copy with ``any_rows``: the
+        dispatch of ``_plin``, whatever the row count)."""
         w = self.gpt.embeddings.word_embeddings.weight
         logits = None
         if self.fused_decode and topo.mp_world_size() == 1:
             from ....ops import gemm as G
-            if h.shape[0] <= self.fused_decode_rows:
+            # the prefill's head: fused_decode_rows deliberately does not gate it (it bounds
+            # the decode step's rows; the prefill dispatches by row count alone, as _plin)
+            if any_rows and q8 is not None:
+                logits = _plin(G, h, None, G.GV_BIAS, q8)
+            if logits is None and h.shape[0] <= self.fused_decode_rows:
                 if q8 is not None:
                     logits = _qlin(G, h.contiguous(), q8)
                 if logits is None and h.shape[0] > 16:
@@ -958,6 +1026,14 @@ class GPTForGeneration(torch.nn.Module):
         return logits.float()
 
     # ---- prefill
+    def _w8_prefill(self):
+        """The copies the prefill runs on: the target's under an active
+        ``weight_quant_prefill``, else None (the 16-bit path, bit for bit)."""
+        return self._w8 if self.weight_quant_prefill else None
+
+    def _prefill_logits(self, last, q8):
+        return self._logits(last) if q8 is None else self._logits(last, q8["head"], any_rows=True)
+
     def _prompt_logits(self, input_ids, lens, cache, lens32):
         """Prefill of the right-padded prompts into an empty ``cache`` and the
         fp32 logits of each row's last token: in one pass, or, for prompts
@@ -968,11 +1044,15 @@ class GPTForGeneration(torch.nn.Module):
             return self._prefill_at(input_ids, lens, [0] * B, cache)
         pos = torch.arange(S, device=dev).unsqueeze(0).expand(B, S)
         x = self.gpt.embeddings(input_ids, pos)
+        q8 = self._w8_prefill()
         for li, layer in enumerate(self.gpt.layers):
-            x = _layer_prefill(layer, x, cache, li, lens32)
+            if q8 is not None and _fusable(layer):
+                x = _layer_prefill(layer, x, cache, li, lens32, q8["layers"][li])
+            else:
+                x = _layer_prefill(layer, x, cache, li, lens32)
         x = self.gpt.final_ln(x)
         last = x[torch.arange(B, device=dev), lens - 1]
-        return self._logits(last)
+        return self._prefill_logits(last, q8)
 
     def _prefill_at(self, tok, count, start, cache):
         """Prefill ``count[b]`` tokens ``tok[b, :count[b]]`` (right-padded
@@ -993,6 +1073,7 @@ class GPTForGeneration(torch.nn.Module):
         ar = torch.arange(B, device=dev)
         last_pos = count - 1
         last = None
+        q8 = self._w8_prefill()
         for c in range(-(-S // N)):
             n = min(N, S - c * N)
             q_starts = start_t + c * N
@@ -1005,11 +1086,15 @@ class GPTForGeneration(torch.nn.Module):
             x = self.gpt.embeddings(tok[:, c * N:c * N + n], pos)
             q32 = q_starts.to(torch.int32)
             for li, layer in enumerate(self.gpt.layers):
-                x = _layer_prefill_at(layer, x, cache, li, q32, kv_lens, rows, keep)
+                if q8 is not None and _fusable(layer):
+                    x = _layer_prefill_at(layer, x, cache, li, q32, kv_lens, rows, keep,
+                                          q8["layers"][li])
+                else:
+                    x = _layer_prefill_at(layer, x, cache, li, q32, kv_lens, rows, keep)
             here = (last_pos >= c * N) & (last_pos < c * N + n)
             xl = x[ar, (last_pos - c * N).clamp(0, n - 1)]
             last = xl if last is None else torch.where(here[:, None], xl, last)
-        return self._logits(self.gpt.final_ln(last))
+        return self._prefill_logits(self.gpt.final_ln(last), q8)
 
     def new_session(self, batch_size, max_len=None):
         """A ``GenerationSession`` of ``batch_size`` rows whose cache holds

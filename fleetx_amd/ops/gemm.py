@@ -682,3 +682,76 @@ def decode_gemm_mx4(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, qkv_cache=N
     if wscale is None:
         return None
     return _decode_gemm(x, wq, wscale, bias, epi, res, qkv_cache, shape, fmt="mxfp4")
+
+
+# ----------------------------------------------------------------------------
+# the quantised copies at 65 rows and more (csrc/kernels/prefill_gemm.hip: a
+# tiled GEMM with the weight operand stationary in registers and the
+# activations staged through LDS; GV_BIAS / GV_GELU / GV_RES, no QKV scatter)
+# ----------------------------------------------------------------------------
+def _prefill_gemm(x, w, wscale, bias, epi, res, shape, fmt):
+    """The body of ``prefill_gemm_w8`` / ``prefill_gemm_w4`` /
+    ``prefill_gemm_mx4``, after ``_decode_gemm``: the checks, the output and
+    the call.  None for a call the kernel does not cover; a malformed residual
+    asserts."""
+    if wscale is None or epi not in (GV_BIAS, GV_GELU, GV_RES):
+        return None
+    if not x.is_cuda or x.dim() != 2 or x.shape[0] < 65 \
+            or x.dtype not in (torch.bfloat16, torch.float16):
+        return None
+    M, K = x.shape
+    wdtype, wpack = _WFMT[fmt][:2]
+    if w.dim() != 2 or w.dtype != wdtype or not w.is_cuda or w.shape[1] * wpack != K:
+        return None
+    N = w.shape[0]
+    if w.stride(1) != 1 or x.stride(1) != 1 or K % 1024 or x.stride(0) % 8 \
+            or (w.stride(0) * w.element_size()) % 16 or w.data_ptr() % 16 or x.data_ptr() % 16:
+        return None
+    if not _wscale_ok(fmt, wscale, N, K):
+        return None
+    if bias is not None and (bias.dtype != x.dtype or bias.numel() != N
+                             or not bias.is_contiguous()):
+        return None
+    y = torch.empty(M, N, device=x.device, dtype=x.dtype)
+    if epi == GV_RES:
+        assert res is not None and res.shape == (M, N) and res.stride(1) == 1 \
+            and res.dtype == x.dtype
+    mt, nt = shape if shape is not None else (0, 0)
+    nb = getattr(_lib.kernels(), "prefill_gemm" + _WFMT[fmt][4])(
+        _lib.dt_code(x.dtype), int(epi), M, N, K, x.data_ptr(), x.stride(0), w.data_ptr(),
+        w.stride(0), wscale.data_ptr(), _lib.ptr(bias), _lib.ptr(res) if epi == GV_RES else 0,
+        res.stride(0) if epi == GV_RES else 0, y.data_ptr(), y.stride(0), int(mt), int(nt),
+        _lib.stream())
+    if nb == 0:
+        return None
+    _lib.maybe_sync()
+    return y
+
+
+def prefill_gemm_w8(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, shape=None):
+    """``x [M, K] @ (wq[N, K] * wscale[N, None])^T`` for M >= 65 rows on the
+    int8 copy ``decode_linear_w8`` streams, with the epilogue ``epi``: GV_BIAS
+    (+b), GV_GELU (gelu_tanh(+b)) or GV_RES (+b + res[M, N]); GV_QKV is not
+    covered (the caller writes K / V itself).  fp32 accumulation, no K split:
+    the bits of an output row depend on that row of ``x`` alone, not on its
+    index, on M, on the other rows or on the launch shape -- they are not the
+    bits ``decode_linear_w8`` / ``decode_gemm_w8`` give it, which split K.
+
+    ``shape = (mt, nt)`` pins the launch shape (16 * mt rows and 64 * nt columns
+    per block; mt in 4, 8, nt in 1, 2, 4) for tests and ``tools/bench_gemv.py``;
+    None: the library's rule.
+
+    Returns the output, or None when the kernel does not cover the call (the
+    caller then uses the 16-bit weight)."""
+    return _prefill_gemm(x, wq, wscale, bias, epi, res, shape, "int8")
+
+
+def prefill_gemm_w4(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, shape=None):
+    """``prefill_gemm_w8`` on the int4 copy (group size 256) of
+    ``decode_linear_w4``; it has no (8, 4) tile."""
+    return _prefill_gemm(x, wq, wscale, bias, epi, res, shape, "int4")
+
+
+def prefill_gemm_mx4(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, shape=None):
+    """``prefill_gemm_w8`` on the MXFP4 copy of ``decode_linear_mx4``."""
+    return _prefill_gemm(x, wq, wscale, bias, epi, res, shape, "mxfp4")

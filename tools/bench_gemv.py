@@ -7,6 +7,7 @@ hipBLASLt (F.linear) on the same operands.
     python tools/bench_gemv.py --w4 [--m 1 4 16] [--repeat 2]
     python tools/bench_gemv.py --mx4 [--m 1 4 16 32 64] [--repeat 3]
     python tools/bench_gemv.py --rows 17 32 48 64 [--shape nt,ks | --sweep]
+    python tools/bench_gemv.py --prefill 65 128 512 2048 [--shape mt,nt | --sweep] [--repeat 3]
 
 ``--w8`` times the weight-only int8 GEMV (csrc/kernels/decode_gemv_w8.hip)
 against the 16-bit one, alternating in one process on weights streamed from
@@ -19,7 +20,9 @@ weights, the two series alternating; its records carry ``w4_us`` / ``mx4_us``.
 ``--rows`` times the skinny GEMM of 17..64 rows (csrc/kernels/decode_gemm.hip)
 in its three formats against the chain it replaces (the vendor GEMM with bias
 and the layer's separate GeLU / residual launch), the same way; ``--shape``
-pins its launch shape and ``--sweep`` times every shape the library has."""
+pins its launch shape and ``--sweep`` times every shape the library has.
+``--prefill`` does the same for the quantised prefill GEMM of 65 rows and more
+(csrc/kernels/prefill_gemm.hip; ``--shape mt,nt``), medians of ``--repeat``."""
 import argparse
 import json
 import os
@@ -178,8 +181,66 @@ def main_rows(args, G):
         torch.cuda.empty_cache()
 
 
+PREFILL_SHAPES = ["1.3B_qkv", "1.3B_out", "1.3B_fc1", "1.3B_fc2", "6.7B_qkv", "6.7B_out",
+                  "6.7B_fc1", "6.7B_fc2", "lm_head_1.3B"]
+
+
+def main_prefill(args, G):
+    """The quantised prefill GEMM (csrc/kernels/prefill_gemm.hip) at ``--prefill``
+    rows in its three formats against the prefill's chain on the 16-bit weight
+    (the vendor GEMM with bias and the separate GeLU / residual launch), the
+    series alternating in one process; medians of ``--repeat`` runs."""
+    from fleetx_amd import ops
+    pins = [tuple(int(v) for v in args.shape.split(","))] if args.shape else [None]
+    if args.sweep:
+        pins = [(mt, nt) for mt in (4, 8) for nt in (1, 2, 4)]
+    med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+    for name in args.shapes or PREFILL_SHAPES:
+        N, K = SHAPES[name]
+        # >= 512 MiB of 4-bit weights (2 GiB of 16-bit ones), as --mx4: the smallest set
+        # any series cycles over is twice the 256 MB Infinity Cache, so every call of
+        # every series streams from HBM
+        ncopy = max(2, -(-(1 << 31) // (N * K * 2)))
+        ws = [(torch.randn(N, K, device="cuda") * K ** -0.5).bfloat16() for _ in range(ncopy)]
+        qs = {"w8": ([ops.quantize_weight_int8(w) for w in ws], G.prefill_gemm_w8),
+              "w4": ([ops.quantize_weight_int4(w) for w in ws], G.prefill_gemm_w4),
+              "mx4": ([ops.quantize_weight_mxfp4(w) for w in ws], G.prefill_gemm_mx4)}
+        b = torch.randn(N, device="cuda").bfloat16()
+        epi = G.GV_GELU if "fc1" in name else G.GV_RES if "out" in name or "fc2" in name \
+            else G.GV_BIAS
+        for M in args.prefill:
+            x = torch.randn(M, K, device="cuda").bfloat16()
+            res = torch.randn(M, N, device="cuda").bfloat16() if epi == G.GV_RES else None
+
+            def chain(i):
+                y = F.linear(x, ws[i], b)
+                if epi == G.GV_GELU:
+                    y = F.gelu(y, approximate="tanh")
+                elif epi == G.GV_RES:
+                    y = y + res
+                return y
+            runs = {"chain_us": []}
+            for _ in range(args.repeat):
+                runs["chain_us"].append(time_graph(chain, ncopy, iters=5))
+                for pin in pins:
+                    for tag, (q, f) in qs.items():
+                        call = lambda i: f(x, *q[i], b, epi, res=res, shape=pin)  # noqa: E731
+                        if call(0) is None:
+                            continue
+                        key = "%s_%s_us" % (tag, "rule" if pin is None else "%d_%d" % pin)
+                        runs.setdefault(key, []).append(time_graph(call, ncopy, iters=5))
+            rec = {"shape": name, "M": M, "N": N, "K": K, "epi": epi}
+            rec.update({k: round(med(v), 1) for k, v in runs.items()})
+            print(json.dumps(rec), flush=True)
+        del ws, qs
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--prefill", type=int, nargs="+", default=None,
+                    help="time the quantised prefill GEMM at these row counts (>= 65); "
+                         "--shape mt,nt pins its launch shape, --sweep times every one")
     ap.add_argument("--m", type=int, nargs="+", default=[1, 16])
     ap.add_argument("--warm", action="store_true",
                     help="also time a weight resident in the Infinity Cache")
@@ -195,6 +256,8 @@ def main():
     ap.add_argument("--sweep", action="store_true", help="--rows: every launch shape")
     args = ap.parse_args()
     from fleetx_amd.ops import gemm as G
+    if args.prefill:
+        return main_prefill(args, G)
     if args.rows:
         return main_rows(args, G)
     if args.mx4:

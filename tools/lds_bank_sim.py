@@ -122,10 +122,28 @@ def check_frag():
               % (D, test(D, off)))
 
 
+def check_prefill_gemm():
+    """The x stage of ``csrc/kernels/prefill_gemm.hip``: rows of 128 bytes
+    (eight 16-byte pieces), lane (r, g) = (lane % 16, lane / 16) reads pieces
+    2 g and 2 g + 1 of row 16 mt + r with ``ds_read_b128``.  Checks that the
+    kernel's swizzle ``slot = piece ^ f(row)`` (``pg_swz``: f = bit 1 of the
+    row | bit 2 of the row << 2) is conflict-free."""
+    def worst(f):
+        return max(cost_b128([128 * (l & 15) + 16 * ((2 * (l >> 4) + i) ^ f(l & 15))
+                              for l in range(64)]) for i in (0, 1))
+    print("prefill_gemm x stage naive:", worst(lambda r: 0), "cycles (ideal 4)")
+    kernel = worst(lambda r: ((r >> 1) & 1) | (((r >> 2) & 1) << 2))
+    print("pg_swz:", kernel, "cycles")
+    assert kernel == 4
+
+
 if __name__ == "__main__":
     import sys
     if "--check-frag" in sys.argv:
         check_frag()
+        sys.exit(0)
+    if "--prefill-gemm" in sys.argv:
+        check_prefill_gemm()
         sys.exit(0)
     for D in (64, 128):
         print("D=%d naive" % D, test(D, make_off(D, (0,) * ((D // 8).bit_length() - 1))))
