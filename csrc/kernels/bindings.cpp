@@ -299,6 +299,20 @@ PYBIND11_MODULE(_kernels, m) {
                                  P(out), F(ws), B, W, H, D, maxlen, nsplit, sqb, sqh, skb, sks,
                                  skh, sob, scale, nw, S(st));
   });
+  m.def("kv_append_fp8", [](int dt, ptr ks, ptr vs, long ssr, long ssh, int B, int S_, int H,
+                            int D, ptr pos, ptr kc, ptr vc, long scb, long scs, long sch,
+                            int maxlen, ptr st) {
+    return fx_kv_append_fp8(dt, CP(ks), CP(vs), ssr, ssh, B, S_, H, D,
+                            reinterpret_cast<const int*>(pos), P(kc), P(vc), scb, scs, sch,
+                            maxlen, S(st));
+  });
+  m.def("decode_attn_fp8", [](int dt, ptr q, ptr kc, ptr vc, ptr out, ptr lens, int B, int H,
+                              int D, int maxlen, int nsplit, ptr ws, long sqb, long sqh, long skb,
+                              long sks, long skh, long sob, float scale, int nw, ptr st) {
+    return fx_decode_attn_fp8(dt, CP(q), CP(kc), CP(vc), P(out),
+                              reinterpret_cast<const int*>(lens), B, H, D, maxlen, nsplit, F(ws),
+                              sqb, sqh, skb, sks, skh, sob, scale, nw, S(st));
+  });
   m.def("softmax_fwd", [](int dt, int mdt, ptr x, ptr mask, ptr y, long rows, int Sq, int Sk,
                           long mask_div, float scale, int causal, ptr st) {
     return fx_softmax_fwd(dt, mdt, CP(x), CP(mask), P(y), rows, Sq, Sk, mask_div, scale, causal,

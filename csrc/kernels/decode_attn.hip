@@ -513,3 +513,12 @@ extern "C" int fx_window_decode_attn(int dt, const void* q, const void* kc, cons
   if (nsplit > 1) mq_combine(dt, D, B * W * H, ws, out, H, nsplit, sob, st);
   return 0;
 }
+
+// decode_attn_combine_kernel for a split-K pass that lives in another file
+// (kv_fp8.hip): merges the nsplit partials [n][nsplit][D + 2] of n = rows * H
+// (row, head) pairs into out.  dt: 0 bf16 / 1 fp16; D: 64 / 128 (the caller's
+// to keep).
+extern "C" void fx_decode_attn_combine(int dt, int D, int n, const float* ws, void* out, int H,
+                                       int nsplit, long sob, hipStream_t st) {
+  mq_combine(dt, D, n, ws, out, H, nsplit, sob, st);
+}

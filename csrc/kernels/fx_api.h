@@ -108,6 +108,12 @@ int fx_beam_decode_attn(int, const void*, const void*, const void*, const int*, 
 int fx_window_decode_attn(int, const void*, const void*, const void*, const int*, void*, float*,
                           int, int, int, int, int, int, long, long, long, long, long, long, float,
                           int, hipStream_t);
+void fx_decode_attn_combine(int, int, int, const float*, void*, int, int, long, hipStream_t);
+int fx_kv_append_fp8(int, const void*, const void*, long, long, int, int, int, int, const int*,
+                     void*, void*, long, long, long, int, hipStream_t);
+int fx_decode_attn_fp8(int, const void*, const void*, const void*, void*, const int*, int, int,
+                       int, int, int, float*, long, long, long, long, long, long, float, int,
+                       hipStream_t);
 void fx_embedding_bwd_sorted(int, const int64_t*, const int64_t*, const void*, float*, int, int,
                              long, long, hipStream_t);
 int fx_softmax_fwd(int, int, const void*, const void*, void*, long, int, int, long, float, int,

@@ -37,7 +37,11 @@ MI355X design (K18/K19):
   that depends only on (seed, token index, row, vocabulary index)
   (``ops.coupled_sample``), so draft and target draw with the same noise and
   the speculative loops above run under ``decode_strategy: sampling`` as they
-  do under greedy search: a draft is accepted iff it equals the target's pick.
+  do under greedy search: a draft is accepted iff it equals the target's pick;
+* ``kv_cache_dtype: fp8_e4m3`` keeps the cache as e4m3 bytes (half the memory
+  and half the bytes a decode step streams): ``ops.kv_append_fp8`` rounds K/V
+  on the way in, ``ops.decode_attention_fp8`` reads them.  Sampling and greedy
+  search in the host loop and under ``device_loop``; the other loops raise.
 """
 import os
 import warnings
@@ -170,9 +174,21 @@ def _topk_ties_low(x, k):
 # ----------------------------------------------------------------------------
 # cached decoding
 # ----------------------------------------------------------------------------
+KV_FP8 = "fp8_e4m3"   # Generation.kv_cache_dtype: an e4m3 image of the 16-bit cache
+
+
 class KVCache:
-    def __init__(self, num_layers, batch, max_len, heads, head_dim, dtype, device):
-        self.k = [torch.zeros(batch, max_len, heads, head_dim, dtype=dtype, device=device)
+    """Per-layer K / V ``[batch, max_len, heads, head_dim]`` of ``dtype``, or
+    with ``kv_dtype = "fp8_e4m3"`` of uint8: every element rounded to e4m3
+    (``ops.kv_append_fp8``: clamp to +-448, nearest even, no scales), half the
+    bytes, read by ``ops.decode_attention_fp8``."""
+
+    def __init__(self, num_layers, batch, max_len, heads, head_dim, dtype, device, kv_dtype=None):
+        if kv_dtype not in (None, KV_FP8):
+            raise ValueError("kv_dtype must be None or %r (got %r)" % (KV_FP8, kv_dtype))
+        self.fp8 = kv_dtype == KV_FP8
+        self.k = [torch.zeros(batch, max_len, heads, head_dim,
+                              dtype=torch.uint8 if self.fp8 else dtype, device=device)
                   for _ in range(num_layers)]
         self.v = [torch.zeros_like(t) for t in self.k]
         self.max_len = max_len
@@ -232,17 +248,35 @@ def _attend(cache, li, q, lens_after):
     return ops.decode_attention(q, cache.k[li], cache.v[li], lens_after)
 
 
+def _is_fp8(cache):
+    return getattr(cache, "fp8", False)
+
+
+def _append_attend_fp8(cache, li, qkv5, pos, lens_after):
+    """The decode step on an e4m3 cache from the packed ``qkv5`` [B, H, 3, D]:
+    K / V rounded and appended at ``pos`` [B] (int32), then the attention of
+    the q view over the one-byte cache; no copy of q, k or v."""
+    ops.kv_append_fp8(qkv5[:, :, 1], qkv5[:, :, 2], cache.k[li], cache.v[li], pos)
+    return ops.decode_attention_fp8(qkv5[:, :, 0], cache.k[li], cache.v[li], lens_after)
+
+
 def _layer_prefill(layer, x, cache, li, lens, w8=None):
     """Full-prompt pass of one decoder layer that also fills the KV cache.
     ``w8`` (``weight_quant_prefill``): this layer's quantised copies; its four
-    linears then run on them (``_qkv_quant``, ``_layer_tail_quant``)."""
+    linears then run on them (``_qkv_quant``, ``_layer_tail_quant``).  An e4m3
+    cache takes the rounded K / V (``ops.kv_append_fp8``) while the prompt's own
+    attention reads the fresh 16-bit K / V: a prompt token attends to unrounded
+    keys, every later token to rounded ones."""
     attn = layer.attn
     h = layer.ln1(x)
     qkv = attn.qkv_proj(h) if w8 is None else _qkv_quant(layer, h, w8)
     b, s = qkv.shape[0], qkv.shape[1]
     qkv5 = qkv.view(b, s, attn.heads, 3, attn.head_dim)
-    cache.k[li][:, :s] = qkv5[:, :, :, 1]
-    cache.v[li][:, :s] = qkv5[:, :, :, 2]
+    if _is_fp8(cache):
+        ops.kv_append_fp8(qkv5[:, :, :, 1], qkv5[:, :, :, 2], cache.k[li], cache.v[li])
+    else:
+        cache.k[li][:, :s] = qkv5[:, :, :, 1]
+        cache.v[li][:, :s] = qkv5[:, :, :, 2]
     o = ops.flash_attention(qkv5[:, :, :, 0], qkv5[:, :, :, 1], qkv5[:, :, :, 2], causal=True,
                             kv_lens=lens).reshape(b, s, -1)
     if w8 is not None:
@@ -342,14 +376,17 @@ def _layer_decode(layer, x, cache, li, pos, lens_after, rows=None):
     qkv = attn.qkv_proj(h)
     b = qkv.shape[0]
     qkv5 = qkv.view(b, attn.heads, 3, attn.head_dim)
-    ar = torch.arange(b, device=x.device) if rows is None else rows.long()
-    kc, vc = _gen_kv(cache, li)
-    kc[ar, pos] = qkv5[:, :, 1]
-    vc[ar, pos] = qkv5[:, :, 2]
-    if rows is None:
-        o = _attend(cache, li, qkv5[:, :, 0].contiguous(), lens_after)
+    if _is_fp8(cache):
+        o = _append_attend_fp8(cache, li, qkv5, pos, lens_after)
     else:
-        o = ops.window_decode_attention(qkv5[:, :, 0].contiguous(), kc, vc, lens_after)
+        ar = torch.arange(b, device=x.device) if rows is None else rows.long()
+        kc, vc = _gen_kv(cache, li)
+        kc[ar, pos] = qkv5[:, :, 1]
+        vc[ar, pos] = qkv5[:, :, 2]
+        if rows is None:
+            o = _attend(cache, li, qkv5[:, :, 0].contiguous(), lens_after)
+        else:
+            o = ops.window_decode_attention(qkv5[:, :, 0].contiguous(), kc, vc, lens_after)
     a, ab = attn.out_proj(o.reshape(b, 1, -1))
     x2, h2 = ops.add_layer_norm(a, ab, x, layer.ln2.weight, layer.ln2.bias, layer.ln2.eps)
     m, mb = layer.mlp(h2)
@@ -475,7 +512,10 @@ def _layer_decode_fused(layer, x, cache, li, pos, lens_after, w8=None, rows=None
     ``qkv_proj`` / ``out_proj`` / ``fc1`` / ``fc2`` to this layer's quantised copies.
     Window form (``rows`` int32 [B*W]): the QKV epilogue appends row ``m`` to
     ``cache[rows[m], pos[m]]`` and the attention is the window kernel with
-    ``lens_after`` [B] keys before the window."""
+    ``lens_after`` [B] keys before the window.
+    On an e4m3 cache (``kv_cache_dtype``; ``pos`` int32, no window form): LN1 ->
+    [QKV GEMV + bias, packed] -> ``_append_attend_fp8`` -> the same tail, i.e.
+    the append and, up to 4 rows, LN1 are launches the 16-bit layer does not have."""
     from ....ops import gemm as G
     attn, mlp = layer.attn, layer.mlp
     w8 = w8 or {}
@@ -483,17 +523,28 @@ def _layer_decode_fused(layer, x, cache, li, pos, lens_after, w8=None, rows=None
     x2d = x.reshape(B, h)
     kv = _gen_kv(cache, li) + ((pos,) if rows is None else (pos, rows))
     ln_fuse = _LN_FUSE and B <= 16
-    q = _dlin(G, x2d, attn.qkv_proj, G.GV_QKV, w8.get("qkv_proj"), qkv_cache=kv,
-              ln=(layer.ln1.weight, layer.ln1.bias, layer.ln1.eps)) if ln_fuse else None
-    if q is None:
-        q = _dlin(G, layer.ln1(x2d), attn.qkv_proj, G.GV_QKV, w8.get("qkv_proj"), qkv_cache=kv)
-    if q is None:
-        return None
-    if rows is None:
-        o = _attend(cache, li, q.view(B, attn.heads, attn.head_dim), lens_after)
+    if _is_fp8(cache):
+        # the QKV epilogue writes a 16-bit cache: the GEMV stores the packed [B, 3h] instead
+        # (GV_BIAS, every weight format; it has no LayerNorm prologue, so LN1 is a launch),
+        # then the quantising append and the fp8 attention
+        y = _dlin(G, layer.ln1(x2d), attn.qkv_proj, G.GV_BIAS, w8.get("qkv_proj"))
+        if y is None:
+            return None
+        o = _append_attend_fp8(cache, li, y.view(B, attn.heads, 3, attn.head_dim), pos,
+                               lens_after)
     else:
-        o = ops.window_decode_attention(q.view(B, attn.heads, attn.head_dim), kv[0], kv[1],
-                                        lens_after)
+        q = _dlin(G, x2d, attn.qkv_proj, G.GV_QKV, w8.get("qkv_proj"), qkv_cache=kv,
+                  ln=(layer.ln1.weight, layer.ln1.bias, layer.ln1.eps)) if ln_fuse else None
+        if q is None:
+            q = _dlin(G, layer.ln1(x2d), attn.qkv_proj, G.GV_QKV, w8.get("qkv_proj"),
+                      qkv_cache=kv)
+        if q is None:
+            return None
+        if rows is None:
+            o = _attend(cache, li, q.view(B, attn.heads, attn.head_dim), lens_after)
+        else:
+            o = ops.window_decode_attention(q.view(B, attn.heads, attn.head_dim), kv[0], kv[1],
+                                            lens_after)
     x2 = _dlin(G, o.view(B, -1), attn.out_proj, G.GV_RES, w8.get("out_proj"), res=x2d)
     f = _dlin(G, x2, mlp.fc1, G.GV_GELU, w8.get("fc1"),
               ln=(layer.ln2.weight, layer.ln2.bias, layer.ln2.eps)) if ln_fuse else None
@@ -825,6 +876,19 @@ class GPTForGeneration(torch.nn.Module):
         self.spec_poll = max(1, int(c.get("spec_poll", 1)))
         if self.spec_device_loop:
             self._spec_check()
+        # the KV cache as e4m3 bytes (None: the model's 16-bit dtype)
+        self.kv_cache_dtype = c.get("kv_cache_dtype")
+        if self.kv_cache_dtype not in (None, KV_FP8):
+            raise ValueError("kv_cache_dtype must be None or %r (got %r)"
+                             % (KV_FP8, self.kv_cache_dtype))
+        if self.kv_cache_dtype is not None:
+            for on, what in ((self.decode_strategy == "beam_search", "beam_search"),
+                             (self.spec_draft is not None or self.spec_device_loop,
+                              "speculative decoding"),
+                             (self.prefill_chunk > 0, "prefill_chunk"),
+                             (topo.mp_world_size() > 1, "tensor parallelism")):
+                if on:
+                    self._no_fp8_kernel(what)
         if self.decode_strategy == "beam_search":
             if self.num_beam_groups > 1:
                 raise ValueError("diverse beam search (num_beam_groups > 1) is not supported yet")
@@ -833,6 +897,16 @@ class GPTForGeneration(torch.nn.Module):
             if self.num_return_sequences > self.num_beams:
                 raise ValueError("num_return_sequences (%d) must not exceed num_beams (%d)"
                                  % (self.num_return_sequences, self.num_beams))
+
+    def _no_fp8_kernel(self, what):
+        raise ValueError("kv_cache_dtype %r: the fp8 KV cache has no kernel for %s yet"
+                         % (self.kv_cache_dtype, what))
+
+    def _new_cache(self, batch, rows, dtype, device):
+        """The ``KVCache`` of a ``generate`` call, in ``kv_cache_dtype``."""
+        attn0 = self.gpt.layers[0].attn
+        return KVCache(len(self.gpt.layers), batch, rows, attn0.heads, attn0.head_dim, dtype,
+                       device, kv_dtype=self.kv_cache_dtype)
 
     def _spec_check(self):
         if not 1 <= self.spec_tokens <= 7:
@@ -868,6 +942,8 @@ class GPTForGeneration(torch.nn.Module):
         draft model close to the target is accepted as often as the coupling
         allows).  ``None`` removes it."""
         if drafter is not None:
+            if self.kv_cache_dtype is not None:
+                self._no_fp8_kernel("speculative decoding")
             self._spec_check()
         self._drafter = drafter
 
@@ -989,6 +1065,8 @@ class GPTForGeneration(torch.nn.Module):
             if topo.mp_world_size() == 1 else self.gpt.embeddings(nxt[:, None], pos[:, None])
         fused = self.fused_decode and x.is_cuda and x.shape[0] <= self.fused_decode_rows
         w8 = q8["layers"] if q8 is not None else None
+        if _is_fp8(cache):
+            wpos = wpos.to(torch.int32)  # once per step: ops.kv_append_fp8 reads int32
         for li, layer in enumerate(self.gpt.layers):
             if fused and _fusable(layer):
                 y = _layer_decode_fused(layer, x, cache, li, wpos, after, w8[li] if w8 else None,
@@ -1100,6 +1178,8 @@ class GPTForGeneration(torch.nn.Module):
         """A ``GenerationSession`` of ``batch_size`` rows whose cache holds
         ``min(max_len or max_position_embeddings, max_position_embeddings)``
         tokens per row; pass it to ``generate(..., session=)`` turn by turn."""
+        if self.kv_cache_dtype is not None:
+            self._no_fp8_kernel("sessions")
         mpe = self.gpt.cfg.max_position_embeddings
         p = next(self.parameters())
         attn0 = self.gpt.layers[0].attn
@@ -1183,11 +1263,12 @@ class GPTForGeneration(torch.nn.Module):
         cfg = self.gpt.cfg
         total = min(int(lens.max().item()) + max_new, cfg.max_position_embeddings)
         p = next(self.parameters())
-        attn0 = self.gpt.layers[0].attn
+        if self.kv_cache_dtype is not None and topo.mp_world_size() > 1:
+            self._no_fp8_kernel("tensor parallelism")
         drafter = self._spec_drafter(B, dev)
         # speculative rounds write spec_tokens rows past the last emitted position
         rows = total + (self.spec_tokens if drafter is not None else 0)
-        cache = KVCache(len(self.gpt.layers), B, rows, attn0.heads, attn0.head_dim, p.dtype, dev)
+        cache = self._new_cache(B, rows, p.dtype, dev)
         gen = None
         if seed is not None:
             gen = torch.Generator(device=dev)

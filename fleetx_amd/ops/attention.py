@@ -282,6 +282,94 @@ def _default_scale(scale, D):
     return scale if scale is not None else 1.0 / math.sqrt(D)
 
 
+# ----------------------------------------------------------------------------
+# FP8 (e4m3) KV cache (csrc/kernels/kv_fp8.hip): the cache is a plain e4m3 image
+# of the 16-bit cache, uint8 [B, maxlen, H, D], no scales
+# ----------------------------------------------------------------------------
+FP8_MAX = 448.0  # largest finite e4m3 value; the append clamps to it (a bare cast gives NaN)
+
+
+def _fp8_bytes(x):
+    """The stored bytes of a 16-bit tensor: ``fp8(clamp(float(x), -448, 448))``."""
+    return x.float().clamp(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn).view(torch.uint8)
+
+
+def kv_append_fp8(k_src, v_src, k_cache, v_cache, pos=None):
+    """Round K / V rows to e4m3 and store them in the uint8 caches
+    ``[B, maxlen, H, D]``.
+
+    ``k_src`` / ``v_src``: ``[B, S, H, D]`` or ``[B, H, D]`` (S = 1), bf16 /
+    fp16, any row and head stride (the k / v views of the packed QKV output
+    need no copy).  Row ``s`` of sample ``b`` goes to position ``(pos[b] if pos
+    is not None else 0) + s``; a position at or past ``maxlen`` is dropped.
+    ``pos`` [B] is read on the device (int32; other integer types are
+    converted), so a captured call follows it.  CPU tensors, and views the
+    16-byte vectors cannot address, take the torch formula."""
+    if k_cache.dtype != torch.uint8 or v_cache.dtype != torch.uint8:
+        raise TypeError("kv_append_fp8: the caches must be uint8 (e4m3 bytes)")
+    if k_src.shape != v_src.shape or k_cache.shape != v_cache.shape:
+        raise ValueError("kv_append_fp8: k / v shapes differ")
+    if k_src.dim() == 3:
+        k_src, v_src = k_src.unsqueeze(1), v_src.unsqueeze(1)
+    B, S, H, D = k_src.shape
+    maxlen = k_cache.shape[1]
+    if k_cache.shape[0] < B or k_cache.shape[2:] != (H, D) \
+            or (pos is not None and pos.shape != (B,)):
+        raise ValueError("kv_append_fp8: cache %s does not take rows of %s"
+                         % (tuple(k_cache.shape), tuple(k_src.shape)))
+    if k_src.is_cuda and k_src.stride() == v_src.stride() and k_src.stride(3) == 1 \
+            and (S == 1 or k_src.stride(0) == S * k_src.stride(1)) \
+            and k_cache.stride() == v_cache.stride() and k_cache.stride(3) == 1:
+        p32 = None if pos is None else pos.to(torch.int32).contiguous()
+        rc = _lib.kernels().kv_append_fp8(
+            _lib.dt_code(k_src.dtype), k_src.data_ptr(), v_src.data_ptr(),
+            k_src.stride(0) if S == 1 else k_src.stride(1),
+            k_src.stride(2), B, S, H, D, _lib.ptr(p32), k_cache.data_ptr(), v_cache.data_ptr(),
+            k_cache.stride(0), k_cache.stride(1), k_cache.stride(2), maxlen, _lib.stream())
+        if rc == 0:
+            _lib.maybe_sync()
+            return
+    dev = k_src.device
+    p = torch.arange(S, device=dev)[None, :] + (0 if pos is None else pos.to(dev).long()[:, None])
+    p = p.expand(B, S)
+    bi, si = (p < maxlen).nonzero(as_tuple=True)
+    k_cache[bi, p[bi, si]] = _fp8_bytes(k_src[bi, si])
+    v_cache[bi, p[bi, si]] = _fp8_bytes(v_src[bi, si])
+
+
+def decode_attention_fp8(q, k_cache, v_cache, lens, scale=None, nsplit=None, nw=None):
+    """``decode_attention`` over an e4m3 KV cache (``kv_append_fp8``).
+
+    q: [B, H, D] bf16 / fp16; caches: uint8 [B, maxlen, H, D]; lens: int32 [B].
+    The bytes are dequantised exactly, scores and sums are fp32 and the output
+    is rounded once, to ``q.dtype``.  ``nw`` pins the waves per workgroup (4 /
+    16; None: 16 under 256 workgroups) for tests and ``tools/bench_decode.py``."""
+    if k_cache.dtype != torch.uint8 or v_cache.dtype != torch.uint8:
+        raise TypeError("decode_attention_fp8: the caches must be uint8 (e4m3 bytes)")
+    B, H, D = q.shape
+    scale = _default_scale(scale, D)
+    if not q.is_cuda:
+        return decode_attention(q, k_cache.view(torch.float8_e4m3fn).float(),
+                                v_cache.view(torch.float8_e4m3fn).float(), lens, scale)
+    maxlen = k_cache.shape[1]
+    ns = nsplit or decode_splits(B, H, maxlen)
+    dt = _lib.dt_code(q.dtype)
+    if q.stride(-1) != 1 or k_cache.stride() != v_cache.stride() or k_cache.stride(-1) != 1:
+        raise ValueError("fp8 decode attention: caches must share a layout with contiguous "
+                         "head dim")
+    out = torch.empty(B, H, D, device=q.device, dtype=q.dtype)
+    ws = torch.empty(B * H * ns * (D + 2), device=q.device, dtype=torch.float32)
+    rc = _lib.kernels().decode_attn_fp8(
+        dt, q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(),
+        lens.to(torch.int32).contiguous().data_ptr(), B, H, D, maxlen, ns, ws.data_ptr(),
+        q.stride(0), q.stride(1), k_cache.stride(0), k_cache.stride(1), k_cache.stride(2),
+        out.stride(0), float(scale), int(nw or 0), _lib.stream())
+    if rc != 0:
+        raise NotImplementedError("fp8 decode attention supports head_dim 64/128 and 16-byte "
+                                  "aligned rows (rc %d)" % rc)
+    return out
+
+
 def _split_k_call(name, q, kv_pairs, ns, call, caches="caches", unsupported=": unsupported shape"):
     """The GPU path the three decode attention wrappers share: dtype and layout
     checks of q ``[R, H, D]`` and the (K, V) cache pairs, ``out`` and the fp32

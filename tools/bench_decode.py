@@ -3,7 +3,7 @@
 Prints one JSON line per case: bytes of K+V cache read / kernel time.  The op
 is HBM bound, so the figure of merit is TB/s against the ~8 TB/s peak.
 
-    python tools/bench_decode.py [--dtype bf16|fp16] [--beam-only] [--window-only]
+    python tools/bench_decode.py [--dtype bf16|fp16] [--beam-only] [--window-only] [--kv-fp8]
 
 Beam cases (``"op": "beam"``): ``ops.beam_decode_attention`` (prompt stored
 once per sample, generated slots through the ancestor table) against
@@ -32,9 +32,13 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--beam-only", action="store_true")
     ap.add_argument("--window-only", action="store_true")
+    ap.add_argument("--kv-fp8", action="store_true",
+                    help="only the e4m3 cache: decode_attention_fp8 against decode_attention")
     a = ap.parse_args()
     from fleetx_amd import ops
     dt = torch.bfloat16 if a.dtype == "bf16" else torch.float16
+    if a.kv_fp8:
+        return kv_fp8_cases(a, dt)
     for B, H, D, L in () if a.beam_only or a.window_only else ((1, 32, 128, 32768), (8, 32, 128, 4096), (32, 32, 128, 2048),
                        (64, 16, 64, 1024), (4, 32, 128, 16384)):
         q = torch.randn(B, H, D, device="cuda", dtype=dt)
@@ -160,6 +164,45 @@ def window_cases(a, dt):
                     "window_over_single": round(us_win / us_one, 2),
                     "W_singles_over_window": round(W * us_one / us_win, 2)}), flush=True)
             del kc, vc
+
+
+def kv_fp8_cases(a, dt):
+    """``"op": "kv_fp8"``: ``ops.decode_attention_fp8`` on the e4m3 image of a
+    cache against ``ops.decode_attention`` on the 16-bit cache (both under
+    graph replay, the two alternated twice, the lower time of each kept), and
+    ``ops.kv_append_fp8`` of one decode row per sample alone.  ``rel_diff`` is
+    between the two outputs, so it carries the e4m3 rounding of K and V."""
+    from fleetx_amd import ops
+    for H, D in ((32, 128), (16, 64)):
+        for B in (1, 32, 64):
+            for L in (512, 2048, 4096):
+                q = torch.randn(B, H, D, device="cuda", dtype=dt)
+                kc, vc = (torch.randn(B, L, H, D, device="cuda", dtype=dt) for _ in range(2))
+                k8, v8 = (torch.empty(B, L, H, D, device="cuda", dtype=torch.uint8)
+                          for _ in range(2))
+                ops.kv_append_fp8(kc, vc, k8, v8)
+                lens = torch.full((B,), L, device="cuda", dtype=torch.int32)
+                pos = torch.full((B,), L - 1, device="cuda", dtype=torch.int32)
+                qkv = torch.randn(B, H, 3, D, device="cuda", dtype=dt)
+                out, ref = ops.decode_attention_fp8(q, k8, v8, lens), ops.decode_attention(
+                    q, kc, vc, lens)
+                err = ((out.float() - ref.float()).norm() / ref.float().norm()).item()
+                us8 = us16 = float("inf")
+                for _ in range(2):
+                    us16 = min(us16, _time(lambda: ops.decode_attention(q, kc, vc, lens), a.iters))
+                    us8 = min(us8, _time(lambda: ops.decode_attention_fp8(q, k8, v8, lens),
+                                         a.iters))
+                us_app = _time(lambda: ops.kv_append_fp8(qkv[:, :, 1], qkv[:, :, 2], k8, v8, pos),
+                               a.iters)
+                nb16 = 2 * B * L * H * D * kc.element_size()
+                print(json.dumps({
+                    "op": "kv_fp8", "B": B, "H": H, "D": D, "context": L, "dtype": a.dtype,
+                    "nsplit": ops.attention.decode_splits(B, H, L), "rel_diff": round(err, 5),
+                    "bf16" if dt == torch.bfloat16 else "fp16": {
+                        "us": round(us16, 1), "TBps": round(nb16 / us16 / 1e6, 3)},
+                    "fp8": {"us": round(us8, 1), "TBps": round(nb16 / 2 / us8 / 1e6, 3)},
+                    "speedup": round(us16 / us8, 2), "append_us": round(us_app, 2)}), flush=True)
+                del kc, vc, k8, v8
 
 
 if __name__ == "__main__":

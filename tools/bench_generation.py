@@ -9,6 +9,7 @@ epilogues).  Random-init weights, bf16.
                                      [--spec-draft int4_g256 --spec-tokens 2 4
                                       [--spec-device-loop]]
                                      [--strategy sampling --sampler coupled]
+                                     [--kv-cache-dtype fp8_e4m3 --prompt 128 2048]
 
 One JSON line per (batch, fused): ms/token, tokens/s and the effective weight
 stream rate (parameter bytes / ms per token).  ``--weight-quant int8`` / ``int4_g256`` (or
@@ -25,10 +26,16 @@ draft steps and one window step), to put another acceptance rate in.
 on the device (``Generation.spec_device_loop``), alternating likewise.
 ``--sampler coupled`` (with ``--strategy sampling``) draws with the coupled
 sampler, under which ``--spec-draft`` applies to sampling as well; every call is
-seeded, so the series of one run emit comparable text."""
+seeded, so the series of one run emit comparable text.
+``--kv-cache-dtype fp8_e4m3`` instead runs the fused series (with whatever else
+the command line sets) in child processes, alternating ``Generation.kv_cache_dtype``
+off and on three times, and prints per (batch, prompt, key) the median ms per
+token with the three values behind it."""
 import argparse
 import json
 import os
+import statistics
+import subprocess
 import sys
 import time
 
@@ -43,7 +50,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="gpt3-1.3B", choices=sorted(MODELS))
     ap.add_argument("--batch", type=int, nargs="+", default=[1, 8, 16])
-    ap.add_argument("--prompt", type=int, default=128)
+    ap.add_argument("--prompt", type=int, nargs="+", default=[128])
     ap.add_argument("--tokens", type=int, default=64)
     ap.add_argument("--fused-only", action="store_true")
     ap.add_argument("--strategy", default="greedy_search",
@@ -72,7 +79,13 @@ def main():
     ap.add_argument("--max-pos", type=int, default=1024, help="max_position_embeddings")
     ap.add_argument("--fused-decode-rows", type=int, default=16, choices=[16, 64],
                     help="Generation.fused_decode_rows: 64 keeps 17..64 rows on the fused layer")
+    ap.add_argument("--kv-cache-dtype", default=None, choices=["fp8_e4m3"],
+                    help="alternate child processes with Generation.kv_cache_dtype off and on")
+    ap.add_argument("--kv-child", default=None, choices=["none", "fp8_e4m3"],
+                    help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.kv_cache_dtype and args.kv_child is None:
+        return kv_cache_series(args)
     from fleetx_amd.models.language_model.gpt.model import GPTConfig, GPTForPretraining
     from fleetx_amd.models.language_model.gpt.generation import GPTForGeneration
     h, L, a = MODELS[args.model]
@@ -83,10 +96,11 @@ def main():
     nbytes = sum(p.numel() * p.element_size() for p in model.parameters())
     if args.session_turns:
         return session_turns(model, args)
-    for B in args.batch:
-        prompt = torch.randint(0, 50304, (B, args.prompt), device="cuda")
+    kv = None if args.kv_child in (None, "none") else args.kv_child
+    for B, P in ((B, P) for P in args.prompt for B in args.batch):
+        prompt = torch.randint(0, 50304, (B, P), device="cuda")
         series = [(f, None, False, 0, False)
-                  for f in ((True,) if args.fused_only else (False, True))]
+                  for f in ((True,) if args.fused_only or args.kv_child else (False, True))]
         series += [(True, wq, False, 0, False) for wq in args.weight_quant]
         if args.device_loop and args.strategy != "beam_search":
             series += [(f, wq, True, 0, False) for f, wq, _, _, _ in series if f]
@@ -100,7 +114,7 @@ def main():
                     "decode_strategy": args.strategy, "num_beams": args.num_beams,
                     "weight_quant": wq, "device_loop": dloop,
                     "fused_decode_rows": args.fused_decode_rows,
-                    "prefill_chunk": args.prefill_chunk}
+                    "prefill_chunk": args.prefill_chunk, "kv_cache_dtype": kv}
             if args.strategy == "sampling":
                 conf.update(sampler=args.sampler, top_k=50, top_p=0.75)
             if spec:
@@ -123,7 +137,8 @@ def main():
             ms = 1e3 * (t - t_pre) / max(1, ids.shape[1] - 1)
             persistent = fused and B <= 4 and \
                 os.environ.get("FLEETX_DECODE_PERSISTENT", "0") == "1"
-            line = {"model": args.model, "batch": B, "strategy": args.strategy,
+            line = {"model": args.model, "batch": B, "prompt": P, "kv_cache_dtype": kv,
+                    "strategy": args.strategy,
                     "sampler": args.sampler if args.strategy == "sampling" else None,
                     "num_beams": args.num_beams if args.strategy == "beam_search" else 1,
                     "fused_decode": fused, "fused_decode_rows": args.fused_decode_rows,
@@ -149,6 +164,27 @@ def main():
             print(json.dumps(line), flush=True)
 
 
+def kv_cache_series(args):
+    """The parent of ``--kv-cache-dtype``: it never opens the GPU itself."""
+    runs = {}
+    for rnd in range(3):
+        for mode in ("none", args.kv_cache_dtype):
+            print("round %d: kv_cache_dtype %s" % (rnd + 1, mode), file=sys.stderr, flush=True)
+            out = subprocess.run([sys.executable, os.path.abspath(__file__)] + sys.argv[1:]
+                                 + ["--kv-child", mode], check=True, stdout=subprocess.PIPE,
+                                 text=True).stdout
+            for line in (json.loads(t) for t in out.splitlines() if t.startswith("{")):
+                key = (line["batch"], line["prompt"], line["weight_quant"], line["device_loop"],
+                       line["kv_cache_dtype"])
+                runs.setdefault(key, (line, []))[1].append(line["ms_per_token"])
+    for line, ms in runs.values():
+        med = statistics.median(ms)
+        line.update(ms_per_token=med, ms_per_token_runs=ms,
+                    tokens_per_s=round(line["batch"] * 1e3 / med, 1))
+        del line["weight_TB_s"], line["prefill_ms"], line["prefill_peak_MiB"]
+        print(json.dumps(line), flush=True)
+
+
 def session_turns(model, args):
     """One JSON line per turn: ms of a turn of ``--turn-tokens`` new tokens on
     the session (prefill of pending + new tokens at the session's offset, one
@@ -168,7 +204,7 @@ def session_turns(model, args):
 
     for B in args.batch:
         s = gen.new_session(B)
-        transcript = torch.randint(0, 50304, (B, args.prompt), device="cuda")
+        transcript = torch.randint(0, 50304, (B, args.prompt[0]), device="cuda")
         gen.generate(transcript, max_length=1, session=s)
         for turn in range(args.session_turns):
             new = torch.randint(0, 50304, (B, args.turn_tokens), device="cuda")
