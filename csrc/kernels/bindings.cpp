@@ -260,6 +260,38 @@ PYBIND11_MODULE(_kernels, m) {
                              reinterpret_cast<const int64_t*>(seed),
                              reinterpret_cast<int64_t*>(ids), F(lse), S(st));
   });
+  // the vocabulary-split forms: `ws` holds sample_split_ws(rows, V) dwords
+  m.def("sample_split_ws", &fx_sample_split_ws);
+  m.def("sample_split", [](int dt, ptr logits, long ld, int B, int V, float inv_temp, int top_k,
+                           float top_p, ptr u, ptr ids, ptr lse, ptr probs, ptr ws, ptr st) {
+    return fx_sample_split(dt, CP(logits), ld, B, V, inv_temp, top_k, top_p, F(u),
+                           reinterpret_cast<int64_t*>(ids), F(lse), F(probs), F(ws), S(st));
+  });
+  m.def("coupled_sample_split", [](ptr logits, long ld, int R, int V, float inv_temp, int top_k,
+                                   float top_p, ptr steps, ptr rows, ptr seed, ptr ids, ptr lse,
+                                   ptr ws, ptr st) {
+    return fx_coupled_sample_split(F(logits), ld, R, V, inv_temp, top_k, top_p,
+                                   reinterpret_cast<const int*>(steps),
+                                   reinterpret_cast<const int*>(rows),
+                                   reinterpret_cast<const int64_t*>(seed),
+                                   reinterpret_cast<int64_t*>(ids), F(lse), F(ws), S(st));
+  });
+  m.def("select_split", [](ptr logits, long ld, int B, int V, int sampling, float inv_temp,
+                           int top_k, float top_p, ptr u, int n_steps, int eos, int pad,
+                           int min_len, float pen, float inv_pen, int bos, int feos,
+                           int feos_step, ptr seen, int words, ptr step, ptr unfinished,
+                           ptr finish_len, ptr scores, ptr out, ptr nxt, ptr cur, ptr lens,
+                           ptr st, ptr seed, ptr ws) {
+    return fx_select_split(F(logits), ld, B, V, sampling, inv_temp, top_k, top_p, F(u), n_steps,
+                           eos, pad, min_len, pen, inv_pen, bos, feos, feos_step,
+                           reinterpret_cast<unsigned int*>(seen), words,
+                           reinterpret_cast<int*>(step), reinterpret_cast<int*>(unfinished),
+                           reinterpret_cast<int*>(finish_len), F(scores),
+                           reinterpret_cast<int64_t*>(out), reinterpret_cast<int64_t*>(nxt),
+                           reinterpret_cast<int64_t*>(cur),
+                           reinterpret_cast<const int64_t*>(lens), S(st),
+                           reinterpret_cast<const int64_t*>(seed), F(ws));
+  });
   m.def("spec_verify", [](ptr logits, long ld, int B, int W, int V, int n_steps, int eos, int pad,
                           int min_len, float pen, float inv_pen, int feos, int feos_step, ptr seen,
                           int words, ptr step, ptr unfinished, ptr finish_len, ptr scores, ptr out,

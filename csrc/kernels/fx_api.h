@@ -92,6 +92,21 @@ int fx_select(const float* logits, long ld_row, int B, int V, int sampling, floa
 int fx_coupled_sample(const float* logits, long ld_row, int R, int V, float inv_temp, int top_k,
                       float top_p, const int* steps, const int* rows, const int64_t* seed,
                       int64_t* out_ids, float* out_lse, hipStream_t);
+// vocabulary-split forms (sampling_split.inc): `ws` holds fx_sample_split_ws(rows, V) dwords
+long fx_sample_split_ws(int R, int V);
+int fx_sample_split(int dtype, const void* logits, long ld_row, int B, int V, float inv_temp,
+                    int top_k, float top_p, const float* uniforms, int64_t* out_ids,
+                    float* out_lse, float* out_probs, float* ws, hipStream_t);
+int fx_coupled_sample_split(const float* logits, long ld_row, int R, int V, float inv_temp,
+                            int top_k, float top_p, const int* steps, const int* rows,
+                            const int64_t* seed, int64_t* out_ids, float* out_lse, float* ws,
+                            hipStream_t);
+int fx_select_split(const float* logits, long ld_row, int B, int V, int sampling, float inv_temp,
+                    int top_k, float top_p, const float* u, int n_steps, int eos, int pad,
+                    int min_len, float pen, float inv_pen, int bos, int feos, int feos_step,
+                    unsigned int* seen, int words, int* step, int* unfinished, int* finish_len,
+                    float* scores, int64_t* out, int64_t* nxt, int64_t* cur, const int64_t* lens,
+                    hipStream_t, const int64_t* seed, float* ws);
 int fx_spec_verify(const float* logits, long ld_row, int B, int W, int V, int n_steps, int eos,
                    int pad, int min_len, float pen, float inv_pen, int feos, int feos_step,
                    unsigned int* seen, int words, int* step, int* unfinished, int* finish_len,

@@ -470,6 +470,25 @@ __device__ __forceinline__ int greedy_row(const L& load, int V, Shared& s, float
   return s.pick < V ? s.pick : 0;
 }
 
+// The host loop's bookkeeping between two decode steps for row `row`, which
+// picked `pick` at step `step` (one thread's plain stores; select_kernel and
+// the split finish kernel).
+__device__ __forceinline__ void select_bookkeep(const SelectArgs& a, const ProcLoad& load,
+                                                unsigned int* seen, int row, int step, int unf,
+                                                int pick, float lse) {
+  const int tok = unf ? pick : a.pad;
+  if (unf) a.scores[row] += load(pick) - lse;
+  a.out[(long)row * a.n_steps + step] = tok;
+  if (tok >= 0 && tok < a.V) seen[tok >> 5] |= 1u << (tok & 31);
+  if (unf && tok == a.eos) {
+    a.unfinished[row] = 0;
+    a.finish_len[row] = step + 1;
+  }
+  a.nxt[row] = tok;
+  a.cur[row] = a.lens[row] + step;
+  a.step[row] = step + 1;
+}
+
 __global__ __launch_bounds__(ST) void select_kernel(SelectArgs a) {
   __shared__ Shared s;
   const int tid = threadIdx.x;
@@ -501,19 +520,7 @@ __global__ __launch_bounds__(ST) void select_kernel(SelectArgs a) {
       pick = greedy_row(load, a.V, s, lse);
     }
   }
-  if (tid == 0) {
-    const int tok = unf ? pick : a.pad;
-    if (unf) a.scores[row] += load(pick) - lse;
-    a.out[(long)row * a.n_steps + step] = tok;
-    if (tok >= 0 && tok < a.V) seen[tok >> 5] |= 1u << (tok & 31);
-    if (unf && tok == a.eos) {
-      a.unfinished[row] = 0;
-      a.finish_len[row] = step + 1;
-    }
-    a.nxt[row] = tok;
-    a.cur[row] = a.lens[row] + step;
-    a.step[row] = step + 1;
-  }
+  if (tid == 0) select_bookkeep(a, load, seen, row, step, unf, pick, lse);
 }
 
 // ------------------------------------------------------ speculative verify
@@ -731,3 +738,7 @@ extern "C" int fx_spec_verify(const float* logits, long ld_row, int B, int W, in
   spec_accept_kernel<<<1, 64, 0, st>>>(a);
   return 0;
 }
+
+// The vocabulary-split forms of sample_kernel, coupled_sample_kernel and
+// select_kernel (fx_sample_split, fx_coupled_sample_split, fx_select_split)
+#include "sampling_split.inc"

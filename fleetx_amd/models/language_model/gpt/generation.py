@@ -630,7 +630,7 @@ class _GraphedSelectStep(_GraphedDecodeStep):
 
     def _run(self):
         logits = self.gen._decode_step(self.nxt, self.cur, self.cache)
-        ops.select_token(logits, self.state)
+        ops.select_token(logits, self.state, split=self.gen.sampler_split)
         return logits
 
 
@@ -801,6 +801,12 @@ class GPTForGeneration(torch.nn.Module):
         if self.sampler not in ("inverse_cdf", "coupled"):
             raise ValueError("sampler must be 'inverse_cdf' or 'coupled' (got %r)"
                              % (self.sampler,))
+        # the sampling picks (host loop, device_loop, the coupled plain loop) by the
+        # vocabulary-split kernels: ops.fused_sample / coupled_sample / select_token, split=True
+        self.sampler_split = c.get("sampler_split", False)
+        if not isinstance(self.sampler_split, bool):
+            raise ValueError("sampler_split must be true or false (got %r)"
+                             % (self.sampler_split,))
         self.temperature = c.get("temperature", 1.0)
         self.top_k = c.get("top_k", 0)
         self.top_p = c.get("top_p", 1.0)
@@ -1372,12 +1378,13 @@ class GPTForGeneration(torch.nn.Module):
             if seed is not None:
                 nxt, lse = ops.coupled_sample(
                     logits, self.temperature, self.top_k, self.top_p, seed,
-                    torch.full((B,), step, dtype=torch.int32, device=dev))
+                    torch.full((B,), step, dtype=torch.int32, device=dev),
+                    split=self.sampler_split)
                 step_score = logits.gather(1, nxt[:, None]).squeeze(1).float() - lse
             elif self.decode_strategy != "greedy_search" and logits.is_cuda:
                 # one fused HIP launch: softmax/T, top-k, top-p, draw, logsumexp
                 nxt, lse = ops.fused_sample(logits, self.temperature, self.top_k, self.top_p,
-                                            generator=gen)
+                                            generator=gen, split=self.sampler_split)
                 step_score = logits.gather(1, nxt[:, None]).squeeze(1).float() - lse
             else:
                 logp = torch.log_softmax(logits, -1)
@@ -1647,7 +1654,7 @@ class GPTForGeneration(torch.nn.Module):
             top_k=self.top_k, top_p=self.top_p, eos=eos, pad=pad, min_len=self.min_length,
             penalty=self.repetition_penalty, forced_bos=self.forced_bos_token_id,
             forced_eos=self.forced_eos_token_id, max_len=max_new, u=u, seed=seed)
-        ops.select_token(logits, state)
+        ops.select_token(logits, state, split=self.sampler_split)
         step = None
         if self.use_hip_graph and dev.type == "cuda":
             step = _GraphedSelectStep(self, cache, state)
@@ -1658,7 +1665,8 @@ class GPTForGeneration(torch.nn.Module):
             if step is not None:
                 step()
             else:
-                ops.select_token(self._decode_step(state.nxt, state.cur, cache), state)
+                ops.select_token(self._decode_step(state.nxt, state.cur, cache), state,
+                                 split=self.sampler_split)
         T = int(state.finish_len.max().item())
         return state.out[:, :T], state.scores
 

@@ -16,6 +16,9 @@ processors, pick, EOS bookkeeping; ``Generation.device_loop``) on a
 ``SelectState``.  ``spec_verify`` is the verify step of a speculative
 round (per-slot processors, picks, acceptance, EOS; ``Generation.spec_device_loop``)
 on a ``SpecState``.
+
+``split=True`` on ``fused_sample``, ``coupled_sample`` and ``select_token``
+takes the vocabulary-split kernels (csrc/kernels/sampling_split.inc).
 """
 import torch
 
@@ -23,13 +26,27 @@ from . import _lib
 from ..parallel import rng
 
 
+def _split_ws(rows, vocab, device):
+    """The workspace of a vocabulary-split call over ``rows`` rows."""
+    return torch.empty(_lib.kernels().sample_split_ws(rows, vocab), device=device,
+                       dtype=torch.float32)
+
+
 def fused_sample(logits, temperature=1.0, top_k=0, top_p=1.0, generator=None,
-                 return_probs=False):
+                 return_probs=False, split=False):
     """Sample one token per row of ``logits`` [B, V] (fp32 or bf16).
 
     Returns ``(ids int64 [B], lse fp32 [B])`` where ``lse`` is the logsumexp of
     the raw logits (the token log-prob is ``logits[ids] - lse``); with
-    ``return_probs`` also the filtered, unnormalised probabilities [B, V]."""
+    ``return_probs`` also the filtered, unnormalised probabilities [B, V].
+
+    ``split`` runs the vocabulary-split kernels (``sampling_split.inc``: the
+    row spread over ``ceil(V / 2048)`` workgroups, then one finish workgroup
+    per row) for ``1 <= top_k <= 64``; they define the kept set on the logits
+    (``x >= x_(k)``, top-p on the mass of strictly larger ``x``) where the
+    default kernel defines it on fp32 probability bits.  Any other ``top_k``
+    is served by the default kernel's phases inside the finish kernel.  CPU
+    tensors ignore ``split``."""
     if logits.dim() != 2:
         raise ValueError("fused_sample expects [B, V] logits")
     B, V = logits.shape
@@ -59,10 +76,13 @@ def fused_sample(logits, temperature=1.0, top_k=0, top_p=1.0, generator=None,
     lse = torch.empty(B, device=dev, dtype=torch.float32)
     probs = torch.empty(B, V, device=dev, dtype=torch.float32) if return_probs else None
     inv_t = 1.0 / float(temperature) if temperature not in (None, 0.0) else 1.0
-    rc = _lib.kernels().sample(dc, logits.data_ptr(), logits.stride(0), B, V, inv_t,
-                               int(top_k or 0), float(1.0 if top_p is None else top_p),
-                               u.data_ptr(), ids.data_ptr(), lse.data_ptr(), _lib.ptr(probs),
-                               _lib.stream())
+    args = (dc, logits.data_ptr(), logits.stride(0), B, V, inv_t, int(top_k or 0),
+            float(1.0 if top_p is None else top_p), u.data_ptr(), ids.data_ptr(),
+            lse.data_ptr(), _lib.ptr(probs))
+    if split:
+        rc = _lib.kernels().sample_split(*args, _split_ws(B, V, dev).data_ptr(), _lib.stream())
+    else:
+        rc = _lib.kernels().sample(*args, _lib.stream())
     if rc != 0:
         raise RuntimeError("fused sampling launch failed ({})".format(rc))
     _lib.maybe_sync()
@@ -109,7 +129,8 @@ def coupled_keys(logits, temperature, top_k, top_p, seed, steps, rows=None, dtyp
     return keys
 
 
-def coupled_sample(logits, temperature, top_k, top_p, seed, steps, rows=None, return_keys=False):
+def coupled_sample(logits, temperature, top_k, top_p, seed, steps, rows=None, return_keys=False,
+                   split=False):
     """The coupled pick of one token per row of ``logits`` [R, V] (fp32): row
     ``r`` chooses token index ``steps[r]`` of noise row ``rows[r]`` (``r``
     itself without ``rows``): ``argmax_i (logits[r, i] / T + g_i)`` over the
@@ -120,7 +141,8 @@ def coupled_sample(logits, temperature, top_k, top_p, seed, steps, rows=None, re
 
     Returns ``(ids int64 [R], lse fp32 [R])`` as ``fused_sample`` does; with
     ``return_keys`` also the formula's keys [R, V] (``coupled_keys``).  CPU
-    tensors take the formula."""
+    tensors take the formula.  ``split``: the vocabulary-split kernels, as in
+    ``fused_sample``."""
     if logits.dim() != 2:
         raise ValueError("coupled_sample expects [R, V] logits")
     R, V = logits.shape
@@ -143,10 +165,14 @@ def coupled_sample(logits, temperature, top_k, top_p, seed, steps, rows=None, re
     ids = torch.empty(R, device=dev, dtype=torch.int64)
     lse = torch.empty(R, device=dev, dtype=torch.float32)
     inv_t = 1.0 / float(temperature) if temperature not in (None, 0.0) else 1.0
-    rc = _lib.kernels().coupled_sample(
-        logits.data_ptr(), logits.stride(0), R, V, inv_t, int(top_k or 0),
-        float(1.0 if top_p is None else top_p), steps.data_ptr(), _lib.ptr(rows),
-        seed.data_ptr(), ids.data_ptr(), lse.data_ptr(), _lib.stream())
+    args = (logits.data_ptr(), logits.stride(0), R, V, inv_t, int(top_k or 0),
+            float(1.0 if top_p is None else top_p), steps.data_ptr(), _lib.ptr(rows),
+            seed.data_ptr(), ids.data_ptr(), lse.data_ptr())
+    if split:
+        rc = _lib.kernels().coupled_sample_split(*args, _split_ws(R, V, dev).data_ptr(),
+                                                 _lib.stream())
+    else:
+        rc = _lib.kernels().coupled_sample(*args, _lib.stream())
     if rc != 0:
         raise RuntimeError("coupled sampling launch failed ({})".format(rc))
     _lib.maybe_sync()
@@ -261,7 +287,7 @@ def processed_logits(logits, state, step=None, seen=None):
     return x
 
 
-def select_token(logits, state):
+def select_token(logits, state, split=False):
     """One step of token selection on the device: the logits processors, the
     pick (greedy, top-k / top-p sampling with ``state.u[step]``, or the coupled
     pick of token index ``step`` under ``state.seed``) and the
@@ -277,7 +303,9 @@ def select_token(logits, state):
     nothing.  Returns ``state.nxt``.
 
     GPU tensors run ``select_kernel`` (a missing extension raises); CPU
-    tensors take the PyTorch formula with the same semantics."""
+    tensors take the PyTorch formula with the same semantics.  ``split``: a
+    sampling pick (either kind) by the vocabulary-split kernels, as in
+    ``fused_sample``; the greedy pick and CPU tensors ignore it."""
     st = state
     if logits.dim() != 2 or logits.shape[1] != st.vocab:
         raise ValueError("select_token expects [B, %d] logits" % st.vocab)
@@ -286,7 +314,7 @@ def select_token(logits, state):
         if logits.dtype != torch.float32 or logits.stride(1) != 1:
             logits = logits.float().contiguous()
         none = lambda t: -1 if t is None else int(t)  # noqa: E731
-        rc = _lib.kernels().select(
+        args = (
             logits.data_ptr(), logits.stride(0), B, V,
             0 if st.greedy else 2 if st.coupled else 1,
             1.0 / st.temperature, st.top_k, st.top_p, _lib.ptr(st.u), st.n_steps, none(st.eos),
@@ -296,6 +324,10 @@ def select_token(logits, state):
             st.unfinished.data_ptr(), st.finish_len.data_ptr(), st.scores.data_ptr(),
             st.out.data_ptr(), st.nxt.data_ptr(), st.cur.data_ptr(), st.lens.data_ptr(),
             _lib.stream(), _lib.ptr(st.seed))
+        if split and not st.greedy:
+            rc = _lib.kernels().select_split(*args, _split_ws(B, V, logits.device).data_ptr())
+        else:
+            rc = _lib.kernels().select(*args)
         if rc != 0:
             raise RuntimeError("token selection launch failed ({})".format(rc))
         _lib.maybe_sync()

@@ -2,6 +2,7 @@
 chain (softmax, topk, sort/cumsum/scatter, multinomial, log_softmax).
 
     python tools/bench_sampling.py [--batch 8 --vocab 50304] [--spec-verify] [--coupled]
+    python tools/bench_sampling.py --calls [--split]
 
 ``--spec-verify``: GPU time of one ``ops.spec_verify`` (the verify step of a
 speculative round: ``spec_pick_kernel`` + ``spec_accept_kernel``) under HIP
@@ -13,7 +14,12 @@ replay does the full work (all drafts accepted).
 coupled pick (mode 2) next to the inverse-CDF one (mode 1), at batch 1 under
 replay, top-k 50 / top-p 0.75.  ``--spec-verify --coupled``: the windows with
 the coupled pick (top-k 50 / top-p 0.75) in place of the greedy one, on the
-same logits (the planted token wins the race as well)."""
+same logits (the planted token wins the race as well).
+
+``--calls``: ``ops.fused_sample``, ``ops.coupled_sample`` and ``ops.select_token``
+modes 1 and 2 under replay at batch 1 / 4 / 16, top-k 50 with top-p 0.75 and
+1.0, one JSON line per (batch, top-p); ``--split`` takes the vocabulary-split
+kernels (``split=True``).  Compare the two in alternating child processes."""
 import argparse
 import json
 import os
@@ -72,6 +78,32 @@ def coupled_bench(V):
     print(json.dumps(line))
 
 
+def calls_bench(V, split):
+    from fleetx_amd import ops
+    n_steps = 64
+    seed = torch.tensor([1234], dtype=torch.int64, device="cuda")
+    for B in (1, 4, 16):
+        ids = torch.randint(0, V, (B, 128), device="cuda")
+        lens = torch.full((B,), 128, device="cuda")
+        lg = 3 * torch.randn(B, V, device="cuda")
+        steps = torch.full((B,), 3, dtype=torch.int32, device="cuda")
+        u = torch.rand(n_steps, B, device="cuda")
+        for top_p in (0.75, 1.0):
+            line = {"vocab": V, "batch": B, "top_k": 50, "top_p": top_p, "split": split}
+            idle = lambda: steps.fill_(3)  # noqa: E731
+            line["fused_sample_us"] = round(graph_us(
+                lambda: ops.fused_sample(lg, 1.0, 50, top_p, split=split), idle), 1)
+            line["coupled_sample_us"] = round(graph_us(
+                lambda: ops.coupled_sample(lg, 1.0, 50, top_p, seed, steps, split=split), idle), 1)
+            for name, kw in (("select_token_mode1_us", dict(u=u)),
+                             ("select_token_mode2_us", dict(seed=seed))):
+                sel = ops.SelectState(ids, lens, V, n_steps, greedy=False, penalty=1.3,
+                                      temperature=1.0, top_k=50, top_p=top_p, **kw)
+                line[name] = round(graph_us(lambda: ops.select_token(lg, sel, split=split),
+                                            lambda: sel.step.fill_(3)), 1)
+            print(json.dumps(line), flush=True)
+
+
 def spec_verify_bench(V, coupled=False):
     from fleetx_amd import ops
     n_steps = 64
@@ -99,7 +131,13 @@ def main():
     ap.add_argument("--vocab", type=int, default=50304)
     ap.add_argument("--spec-verify", action="store_true")
     ap.add_argument("--coupled", action="store_true")
+    ap.add_argument("--calls", action="store_true")
+    ap.add_argument("--split", action="store_true")
     a = ap.parse_args()
+    if a.split and not a.calls:
+        ap.error("--split goes with --calls")
+    if a.calls:
+        return calls_bench(a.vocab, a.split)
     if a.spec_verify:
         return spec_verify_bench(a.vocab, a.coupled)
     if a.coupled:
