@@ -476,6 +476,28 @@ PYBIND11_MODULE(_kernels, m) {
                                ldw, reinterpret_cast<const uint8_t*>(wscale), CP(bias), CP(res),
                                ldres, P(y), ldy, mt, nt, S(st));
   });
+  // W8A8 prefill (prefill_gemm_i8.hip): the row quantiser, the launch rule (mt, nt, ks) and
+  // the int8 MFMA GEMM with its int32 workspace for ks > 1
+  m.def("quant_rows_i8", [](int dt, int M, int K, ptr x, long ldx, ptr xq, ptr sx, ptr st) {
+    return fx_quant_rows_i8(dt, M, K, CP(x), ldx, reinterpret_cast<int8_t*>(xq),
+                            reinterpret_cast<float*>(sx), S(st));
+  });
+  m.def("prefill_i8_rule", [](int M, int N, int K) {
+    int o[3] = {0, 0, 0};
+    fx_prefill_i8_rule(M, N, K, o);
+    return py::make_tuple(o[0], o[1], o[2]);
+  });
+  m.def("prefill_gemm_w8a8", [](int dt, int epi, int M, int N, int K, ptr xq, long ldx, ptr sx,
+                                ptr wq, long ldw, ptr wscale, ptr bias, ptr res, long ldres, ptr y,
+                                long ldy, ptr slab, long slab_elems, int mt, int nt, int ks,
+                                ptr st) {
+    return fx_prefill_gemm_w8a8(dt, epi, M, N, K, reinterpret_cast<const int8_t*>(xq), ldx,
+                                reinterpret_cast<const float*>(sx),
+                                reinterpret_cast<const int8_t*>(wq), ldw,
+                                reinterpret_cast<const float*>(wscale), CP(bias), CP(res), ldres,
+                                P(y), ldy, reinterpret_cast<int*>(slab), slab_elems, mt, nt, ks,
+                                S(st));
+  });
   // CU-masked stream (streams.hip): returns (stream handle, CUs selected)
   m.def("cumask_stream_create", [](int ncu) {
     int got = 0;

@@ -182,6 +182,13 @@ int fx_prefill_gemm_w4(int, int, int, int, int, const void*, long, const uint8_t
 int fx_prefill_gemm_mx4(int, int, int, int, int, const void*, long, const uint8_t*, long,
                         const uint8_t*, const void*, const void*, long, void*, long, int, int,
                         hipStream_t);
+// prefill_gemm_i8.hip: per-row int8 activations and the W8A8 prefill GEMM on the int8 copy;
+// launch shape (mt, nt, ks), 0 0 0: prefill_i8_rule; int32 workspace for ks > 1
+int fx_quant_rows_i8(int, int, int, const void*, long, int8_t*, float*, hipStream_t);
+void fx_prefill_i8_rule(int, int, int, int*);
+int fx_prefill_gemm_w8a8(int, int, int, int, int, const int8_t*, long, const float*, const int8_t*,
+                         long, const float*, const void*, const void*, long, void*, long, int*,
+                         long, int, int, int, hipStream_t);
 hipStream_t fx_cumask_stream_create(int, int*);
 int fx_stream_destroy(hipStream_t);
 int fx_comm_max_world();

@@ -260,16 +260,17 @@ def _append_attend_fp8(cache, li, qkv5, pos, lens_after):
     return ops.decode_attention_fp8(qkv5[:, :, 0], cache.k[li], cache.v[li], lens_after)
 
 
-def _layer_prefill(layer, x, cache, li, lens, w8=None):
+def _layer_prefill(layer, x, cache, li, lens, w8=None, act=None):
     """Full-prompt pass of one decoder layer that also fills the KV cache.
     ``w8`` (``weight_quant_prefill``): this layer's quantised copies; its four
-    linears then run on them (``_qkv_quant``, ``_layer_tail_quant``).  An e4m3
+    linears then run on them (``_qkv_quant``, ``_layer_tail_quant``), with
+    ``act`` (``prefill_act_quant``) on quantised input rows.  An e4m3
     cache takes the rounded K / V (``ops.kv_append_fp8``) while the prompt's own
     attention reads the fresh 16-bit K / V: a prompt token attends to unrounded
     keys, every later token to rounded ones."""
     attn = layer.attn
     h = layer.ln1(x)
-    qkv = attn.qkv_proj(h) if w8 is None else _qkv_quant(layer, h, w8)
+    qkv = attn.qkv_proj(h) if w8 is None else _qkv_quant(layer, h, w8, act)
     b, s = qkv.shape[0], qkv.shape[1]
     qkv5 = qkv.view(b, s, attn.heads, 3, attn.head_dim)
     if _is_fp8(cache):
@@ -280,24 +281,24 @@ def _layer_prefill(layer, x, cache, li, lens, w8=None):
     o = ops.flash_attention(qkv5[:, :, :, 0], qkv5[:, :, :, 1], qkv5[:, :, :, 2], causal=True,
                             kv_lens=lens).reshape(b, s, -1)
     if w8 is not None:
-        return _layer_tail_quant(layer, x, o, w8)
+        return _layer_tail_quant(layer, x, o, w8, act)
     a, ab = attn.out_proj(o)
     x2, h2 = ops.add_layer_norm(a, ab, x, layer.ln2.weight, layer.ln2.bias, layer.ln2.eps)
     m, mb = layer.mlp(h2)
     return ops.bias_dropout_add(m, mb, x2)
 
 
-def _layer_prefill_at(layer, x, cache, li, q_starts, kv_lens, rows, keep, w8=None):
+def _layer_prefill_at(layer, x, cache, li, q_starts, kv_lens, rows, keep, w8=None, act=None):
     """A block of new tokens per sample over a cache that holds their
     predecessors (a prefill chunk, a session turn): x [B, n, h]; token ``i`` of
     row ``b`` sits at position ``q_starts[b] + i`` and its K/V go to cache row
     ``rows[b, i]`` (the same number); ``kv_lens`` [B] keys are valid once the
     block is in.  ``keep``: None, or the (batch, token) index pair of the
     tokens whose cache row exists (padding tokens past the cache are dropped).
-    ``w8``: as in ``_layer_prefill``."""
+    ``w8``, ``act``: as in ``_layer_prefill``."""
     attn = layer.attn
     h = layer.ln1(x)
-    qkv = attn.qkv_proj(h) if w8 is None else _qkv_quant(layer, h, w8)
+    qkv = attn.qkv_proj(h) if w8 is None else _qkv_quant(layer, h, w8, act)
     b, s = qkv.shape[0], qkv.shape[1]
     qkv5 = qkv.view(b, s, attn.heads, 3, attn.head_dim)
     kc, vc = cache.k[li], cache.v[li]
@@ -311,7 +312,7 @@ def _layer_prefill_at(layer, x, cache, li, q_starts, kv_lens, rows, keep, w8=Non
         vc[bi, rows[bi, si]] = qkv5[bi, si, :, 2]
     o = ops.prefill_attention(qkv5[:, :, :, 0], kc, vc, q_starts, kv_lens).reshape(b, s, -1)
     if w8 is not None:
-        return _layer_tail_quant(layer, x, o, w8)
+        return _layer_tail_quant(layer, x, o, w8, act)
     a, ab = attn.out_proj(o)
     x2, h2 = ops.add_layer_norm(a, ab, x, layer.ln2.weight, layer.ln2.bias, layer.ln2.eps)
     m, mb = layer.mlp(h2)
@@ -459,17 +460,25 @@ def _dlin(G, x, lin, epi, q8, **kw):
     return G.decode_linear(x, lin.weight, lin.bias, epi, **kw)
 
 
-def _plin(G, x, lin, epi, q8, res=None):
+def _plin(G, x, lin, epi, q8, res=None, act=None):
     """One linear of the quantised prefill (``weight_quant_prefill``) on ``x``
     [rows, K]: on the quantised copy ``q8``, by row count on the prefill GEMM
     (above 64 rows), the skinny GEMM (17..64) or the decode GEMV (a one-row
     session turn is valid), so the weights do not depend on the row count.  A
     linear without a copy, or a call the kernel does not cover, runs that one
     call on its 16-bit weight as ``_ulin`` does.  ``lin`` None: the LM head,
-    which has no bias and no fallback here (the result may be None)."""
+    which has no bias and no fallback here (the result may be None).  ``act``
+    (``prefill_act_quant``, layer linears only): above 64 rows the rows of ``x``
+    are quantised to int8 and the int8 copy runs on the W8A8 GEMM; a call that
+    declines takes the weight-only prefill GEMM."""
     x = x.contiguous()
     if q8 is not None:
         n = x.shape[0]
+        if act is not None and n > 64 and x.shape[1] % 1024 == 0 and x.shape[1] <= 65536:
+            y = G.prefill_gemm_w8a8(*ops.quantize_rows_int8(x), q8[1], q8[2], lin.bias, epi,
+                                    res=res, out_dtype=x.dtype)
+            if y is not None:
+                return y
         name = q8[0] if n <= 16 else _ROWS_TWIN[q8[0]] if n <= 64 else _PREFILL_TWIN[q8[0]]
         y = getattr(G, name)(x, q8[1], q8[2], lin.bias if lin is not None else None, epi, res=res)
         if y is not None or lin is None:
@@ -477,25 +486,26 @@ def _plin(G, x, lin, epi, q8, res=None):
     return _ulin(G, x, lin, epi, res=res) if lin is not None else None
 
 
-def _qkv_quant(layer, h, w8):
+def _qkv_quant(layer, h, w8, act=None):
     """The packed QKV [B, S, 3 hidden] of the normalised ``h`` [B, S, hidden]
     on the quantised copy; the caller writes K / V and attends as ever."""
     from ....ops import gemm as G
     b, s = h.shape[0], h.shape[1]
     return _plin(G, h.reshape(b * s, -1), layer.attn.qkv_proj, G.GV_BIAS,
-                 w8.get("qkv_proj")).view(b, s, -1)
+                 w8.get("qkv_proj"), act=act).view(b, s, -1)
 
 
-def _layer_tail_quant(layer, x, o, w8):
+def _layer_tail_quant(layer, x, o, w8, act=None):
     """The rest of a prefill layer after the attention output ``o`` on the
     quantised copies: [out-proj + bias + residual] -> LN2 -> [FFN1 + bias +
     GeLU] -> [FFN2 + bias + residual], each one launch."""
     from ....ops import gemm as G
     b, s, hid = x.shape
     x2d = x.reshape(b * s, hid)
-    x2 = _plin(G, o.reshape(b * s, -1), layer.attn.out_proj, G.GV_RES, w8.get("out_proj"), res=x2d)
-    f = _plin(G, layer.ln2(x2), layer.mlp.fc1, G.GV_GELU, w8.get("fc1"))
-    return _plin(G, f, layer.mlp.fc2, G.GV_RES, w8.get("fc2"), res=x2).view(b, s, hid)
+    x2 = _plin(G, o.reshape(b * s, -1), layer.attn.out_proj, G.GV_RES, w8.get("out_proj"), res=x2d,
+               act=act)
+    f = _plin(G, layer.ln2(x2), layer.mlp.fc1, G.GV_GELU, w8.get("fc1"), act=act)
+    return _plin(G, f, layer.mlp.fc2, G.GV_RES, w8.get("fc2"), res=x2, act=act).view(b, s, hid)
 
 
 def _layer_decode_fused(layer, x, cache, li, pos, lens_after, w8=None, rows=None):
@@ -844,6 +854,16 @@ class GPTForGeneration(torch.nn.Module):
         if self.weight_quant_prefill and self.weight_quant is None:
             raise ValueError("weight_quant_prefill needs weight_quant: there are no quantised "
                              "copies to prefill on")
+        # the layer linears of that prefill with their input rows quantised to int8 as well
+        # (W8A8: ops.quantize_rows_int8 + ops.gemm.prefill_gemm_w8a8) at 65 rows and more
+        self.prefill_act_quant = c.get("prefill_act_quant")
+        if self.prefill_act_quant not in (None, "int8"):
+            raise ValueError("prefill_act_quant must be None or 'int8' (got %r)"
+                             % (self.prefill_act_quant,))
+        if self.prefill_act_quant is not None and (self.weight_quant != "int8"
+                                                   or not self.weight_quant_prefill):
+            raise ValueError("prefill_act_quant needs weight_quant: int8 and "
+                             "weight_quant_prefill: true (the int8 copies it multiplies)")
         self._w8 = None        # {"layers": [{name: (GEMV name, q, scale)}], "head": (...)}
         self._w8_src = []      # (weight, _version, data_ptr) of every quantised weight
         self._w8_warned = False
@@ -1131,7 +1151,8 @@ class GPTForGeneration(torch.nn.Module):
         q8 = self._w8_prefill()
         for li, layer in enumerate(self.gpt.layers):
             if q8 is not None and _fusable(layer):
-                x = _layer_prefill(layer, x, cache, li, lens32, q8["layers"][li])
+                x = _layer_prefill(layer, x, cache, li, lens32, q8["layers"][li],
+                                   self.prefill_act_quant)
             else:
                 x = _layer_prefill(layer, x, cache, li, lens32)
         x = self.gpt.final_ln(x)
@@ -1172,7 +1193,7 @@ class GPTForGeneration(torch.nn.Module):
             for li, layer in enumerate(self.gpt.layers):
                 if q8 is not None and _fusable(layer):
                     x = _layer_prefill_at(layer, x, cache, li, q32, kv_lens, rows, keep,
-                                          q8["layers"][li])
+                                          q8["layers"][li], self.prefill_act_quant)
                 else:
                     x = _layer_prefill_at(layer, x, cache, li, q32, kv_lens, rows, keep)
             here = (last_pos >= c * N) & (last_pos < c * N + n)

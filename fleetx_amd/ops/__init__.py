@@ -6,6 +6,7 @@ from .attention import (flash_attention, flash_attention_qkvpacked, attention_re
                        prefill_attention, kv_append_fp8, decode_attention_fp8)
 from .loss_embed import softmax_cross_entropy, embedding  # noqa: F401
 from .quant import fake_quant, quantize_weight_int8, dequantize_weight_int8  # noqa: F401
+from .quant import quantize_rows_int8  # noqa: F401
 from .quant import (quantize_weight_int4, dequantize_weight_int4, pack_int4,  # noqa: F401
                     unpack_int4)
 from .quant import (quantize_weight_mxfp4, dequantize_weight_mxfp4, pack_mxfp4,  # noqa: F401

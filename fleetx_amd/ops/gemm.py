@@ -755,3 +755,68 @@ def prefill_gemm_w4(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, shape=None)
 def prefill_gemm_mx4(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, shape=None):
     """``prefill_gemm_w8`` on the MXFP4 copy of ``decode_linear_mx4``."""
     return _prefill_gemm(x, wq, wscale, bias, epi, res, shape, "mxfp4")
+
+
+# ----------------------------------------------------------------------------
+# W8A8 prefill (csrc/kernels/prefill_gemm_i8.hip): per-row int8 activations
+# (ops.quantize_rows_int8) times the int8 copy on the int8 MFMA, int32 sums
+# ----------------------------------------------------------------------------
+def prefill_gemm_w8a8(xq, sx, wq, wscale, bias=None, epi=GV_BIAS, res=None, out_dtype=None,
+                      shape=None):
+    """``epi(float(xq[M, K] @ wq[N, K]^T) * (sx[:, None] * wscale[None, :]) +
+    bias)`` for M >= 65 rows: ``xq`` int8 / ``sx`` fp32 [M] from
+    ``ops.quantize_rows_int8``, ``wq`` / ``wscale`` the int8 copy
+    ``decode_linear_w8`` streams, ``K % 1024 == 0``, ``K <= 65536``.  The sum is
+    an exact int32 sum (``v_mfma_i32_16x16x64_i8``), the scale product, the
+    multiply, the bias add and the epilogue (GV_BIAS, GV_GELU or GV_RES with
+    ``res [M, N]``) are fp32 and the output is rounded once to ``out_dtype``
+    (bf16 / fp16; default: the dtype of ``bias`` or ``res``, else bf16).  The
+    bits of an output row depend on that row's ``xq`` / ``sx`` alone: not on its
+    index, on M or on the launch shape, K split included.
+
+    ``shape = (mt, nt, ks)`` pins the launch (16 * mt rows and 64 * nt columns
+    per block, ks splits of K across blocks; mt in 4, 8, nt in 1, 2, 4, ks in
+    1, 2, 4) for tests and ``tools/bench_gemv.py``; None: the library's rule.
+
+    Returns the output, or None when the kernel does not cover the call."""
+    if wscale is None or sx is None or epi not in (GV_BIAS, GV_GELU, GV_RES):
+        return None
+    if out_dtype is None:
+        out_dtype = bias.dtype if bias is not None else res.dtype if res is not None \
+            else torch.bfloat16
+    if out_dtype not in (torch.bfloat16, torch.float16):
+        return None
+    if not xq.is_cuda or xq.dim() != 2 or xq.dtype != torch.int8 or xq.shape[0] < 65:
+        return None
+    M, K = xq.shape
+    if wq.dim() != 2 or wq.dtype != torch.int8 or not wq.is_cuda or wq.shape[1] != K:
+        return None
+    N = wq.shape[0]
+    if wq.stride(1) != 1 or xq.stride(1) != 1 or K % 1024 or K > 65536 or xq.stride(0) % 16 \
+            or wq.stride(0) % 16 or wq.data_ptr() % 16 or xq.data_ptr() % 16:
+        return None
+    if not _wscale_ok("int8", wscale, N, K) or not _wscale_ok("int8", sx, M, K):
+        return None
+    if bias is not None and (bias.dtype != out_dtype or bias.numel() != N
+                             or not bias.is_contiguous()):
+        return None
+    if epi == GV_RES:
+        assert res is not None and res.shape == (M, N) and res.stride(1) == 1 \
+            and res.dtype == out_dtype
+    k = _lib.kernels()
+    mt, nt, ks = shape if shape is not None else k.prefill_i8_rule(M, N, K)
+    if mt not in (4, 8) or nt not in (1, 2, 4) or ks not in (1, 2, 4):
+        return None
+    y = torch.empty(M, N, device=xq.device, dtype=out_dtype)
+    nslab = ks * M * ((N + 7) // 8 * 8) if ks > 1 else 0
+    slab = torch.empty(nslab, device=xq.device, dtype=torch.int32) if nslab else None
+    nb = k.prefill_gemm_w8a8(
+        _lib.dt_code(out_dtype), int(epi), M, N, K, xq.data_ptr(), xq.stride(0), sx.data_ptr(),
+        wq.data_ptr(), wq.stride(0), wscale.data_ptr(), _lib.ptr(bias),
+        _lib.ptr(res) if epi == GV_RES else 0, res.stride(0) if epi == GV_RES else 0,
+        y.data_ptr(), y.stride(0), _lib.ptr(slab), nslab, int(mt), int(nt), int(ks),
+        _lib.stream())
+    if nb == 0:
+        return None
+    _lib.maybe_sync()
+    return y

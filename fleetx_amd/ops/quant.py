@@ -64,6 +64,29 @@ def quantize_weight_int8(w):
     return q.contiguous(), scale.contiguous()
 
 
+def quantize_rows_int8(x):
+    """``quantize_weight_int8``'s formula on the rows of an activation ``x
+    [M, K]``: ``sx[m] = max|x[m, :]| / 127`` (fp32, an IEEE division; 1 for an
+    all-zero row) and ``xq = clamp(rint(x / sx), -127, 127)``, ties to even.
+    Returns ``(xq int8 [M, K] contiguous, sx fp32 [M])``, the operands of
+    ``ops.gemm.prefill_gemm_w8a8``.  A bf16 / fp16 GPU tensor with ``K % 1024
+    == 0``, ``K <= 65536`` and rows that admit 16-byte loads runs
+    csrc/kernels/prefill_gemm_i8.hip (one read of ``x``); everything else the
+    torch formula, which gives the same bytes.  Inputs are trusted finite."""
+    assert x.dim() == 2 and x.is_floating_point()
+    M, K = x.shape
+    if x.is_cuda and x.dtype in (torch.bfloat16, torch.float16) and M >= 1 and K % 1024 == 0 \
+            and 0 < K <= 65536 and x.stride(1) == 1 and x.stride(0) % 8 == 0 \
+            and x.stride(0) >= K and x.data_ptr() % 16 == 0 and not x.requires_grad:
+        xq = torch.empty(M, K, device=x.device, dtype=torch.int8)
+        sx = torch.empty(M, device=x.device, dtype=torch.float32)
+        if _lib.kernels().quant_rows_i8(_lib.dt_code(x.dtype), M, K, x.data_ptr(), x.stride(0),
+                                        xq.data_ptr(), sx.data_ptr(), _lib.stream()):
+            _lib.maybe_sync()
+            return xq, sx
+    return quantize_weight_int8(x)
+
+
 def dequantize_weight_int8(q, scale, dtype=torch.float32):
     """``q * scale[:, None]`` computed in fp32 and rounded once to ``dtype``."""
     return (q.float() * scale.float()[:, None]).to(dtype)

@@ -8,6 +8,7 @@ hipBLASLt (F.linear) on the same operands.
     python tools/bench_gemv.py --mx4 [--m 1 4 16 32 64] [--repeat 3]
     python tools/bench_gemv.py --rows 17 32 48 64 [--shape nt,ks | --sweep]
     python tools/bench_gemv.py --prefill 65 128 512 2048 [--shape mt,nt | --sweep] [--repeat 3]
+    python tools/bench_gemv.py --prefill 65 128 512 2048 --w8a8 [--shape mt,nt,ks | --sweep]
 
 ``--w8`` times the weight-only int8 GEMV (csrc/kernels/decode_gemv_w8.hip)
 against the 16-bit one, alternating in one process on weights streamed from
@@ -22,10 +23,17 @@ in its three formats against the chain it replaces (the vendor GEMM with bias
 and the layer's separate GeLU / residual launch), the same way; ``--shape``
 pins its launch shape and ``--sweep`` times every shape the library has.
 ``--prefill`` does the same for the quantised prefill GEMM of 65 rows and more
-(csrc/kernels/prefill_gemm.hip; ``--shape mt,nt``), medians of ``--repeat``."""
+(csrc/kernels/prefill_gemm.hip; ``--shape mt,nt``), medians of ``--repeat``;
+with ``--w8a8`` the W8A8 path (csrc/kernels/prefill_gemm_i8.hip: row quantiser
+plus int8 MFMA GEMM, ``--shape mt,nt,ks``) against the weight-only int8 GEMM and
+the same chain, with the GEMM alone and its int8 MFMA rate; ``--rounds R`` runs
+it as R child processes one after the other, prints the medians over the rounds
+and, as the old-versus-old figure, the spread of the two unchanged series (the
+chain and the weight-only GEMM, each timed twice per child)."""
 import argparse
 import json
 import os
+import subprocess
 import sys
 
 import torch
@@ -236,8 +244,102 @@ def main_prefill(args, G):
         torch.cuda.empty_cache()
 
 
+def main_prefill_i8(args, G):
+    """Quantise + W8A8 GEMM (``q_*``), the GEMM alone on rows quantised once
+    (``g_*``), the weight-only int8 GEMM (``w8_rule_us``) and the 16-bit chain,
+    the series alternating in one process; medians of ``--repeat`` runs."""
+    from fleetx_amd import ops
+    pins = [tuple(int(v) for v in args.shape.split(","))] if args.shape else [None]
+    if args.sweep:
+        pins = [(mt, nt, ks) for mt in (4, 8) for nt in (1, 2, 4) for ks in (1, 2, 4)]
+    med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+    for name in args.shapes or PREFILL_SHAPES:
+        N, K = SHAPES[name]
+        ncopy = max(2, -(-(1 << 30) // (N * K)))   # >= 1 GiB of int8: every call streams from HBM
+        ws = [(torch.randn(N, K, device="cuda") * K ** -0.5).bfloat16() for _ in range(ncopy)]
+        q = [ops.quantize_weight_int8(w) for w in ws]
+        b = torch.randn(N, device="cuda").bfloat16()
+        epi = G.GV_GELU if "fc1" in name else G.GV_RES if "out" in name or "fc2" in name \
+            else G.GV_BIAS
+        for M in args.prefill:
+            x = torch.randn(M, K, device="cuda").bfloat16()
+            xq, sx = ops.quantize_rows_int8(x)
+            res = torch.randn(M, N, device="cuda").bfloat16() if epi == G.GV_RES else None
+
+            def chain(i):
+                y = F.linear(x, ws[i], b)
+                if epi == G.GV_GELU:
+                    y = F.gelu(y, approximate="tanh")
+                elif epi == G.GV_RES:
+                    y = y + res
+                return y
+            runs = {"chain_us": [], "w8_rule_us": [], "quant_us": []}
+            w8 = lambda i: G.prefill_gemm_w8(x, *q[i], b, epi, res=res)  # noqa: E731
+            for _ in range(args.repeat):
+                runs["chain_us"].append(time_graph(chain, ncopy, iters=5))
+                runs["w8_rule_us"].append(time_graph(w8, ncopy, iters=5))
+                runs["quant_us"].append(time_graph(lambda i: ops.quantize_rows_int8(x), ncopy,
+                                                   iters=5))
+                for pin in pins:
+                    kw = dict(res=res, shape=pin)
+                    tag = "rule" if pin is None else "%d_%d_%d" % pin
+                    runs.setdefault("q_%s_us" % tag, []).append(time_graph(
+                        lambda i: G.prefill_gemm_w8a8(*ops.quantize_rows_int8(x), *q[i], b, epi,
+                                                      **kw), ncopy, iters=5))
+                    runs.setdefault("g_%s_us" % tag, []).append(time_graph(
+                        lambda i: G.prefill_gemm_w8a8(xq, sx, *q[i], b, epi, **kw), ncopy,
+                        iters=5))
+                # the two unchanged series once more, after everything else: old versus old
+                runs.setdefault("chain_again_us", []).append(time_graph(chain, ncopy, iters=5))
+                runs.setdefault("w8_again_us", []).append(time_graph(w8, ncopy, iters=5))
+            rec = {"shape": name, "M": M, "N": N, "K": K, "epi": epi}
+            rec.update({k: round(med(v), 1) for k, v in runs.items()})
+            best = min(v for k, v in rec.items() if k.startswith("g_"))
+            rec["gemm_int8_TOPS"] = round(2.0 * M * N * K / best / 1e6, 1)
+            print(json.dumps(rec), flush=True)
+        del ws, q
+        torch.cuda.empty_cache()
+
+
+def rounds_prefill_i8(args):
+    """``--w8a8 --rounds R``: R child processes of the same command, one after
+    the other (a failed child ends the run); per case the medians over the
+    rounds and ``old_spread_pct``, (max - min) / min over the 2 R samples of
+    each unchanged series, the larger of the two."""
+    cmd = [sys.executable, os.path.abspath(__file__)] + [a for a in sys.argv[1:]]
+    i = cmd.index("--rounds")
+    del cmd[i:i + 2]
+    got = {}
+    for _ in range(args.rounds):
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+        if r.returncode != 0:
+            raise SystemExit("child failed (%d):\n%s" % (r.returncode, r.stderr[-3000:]))
+        for ln in r.stdout.splitlines():
+            if ln.startswith("{"):
+                rec = json.loads(ln)
+                got.setdefault((rec["shape"], rec["M"]), []).append(rec)
+    med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+    for recs in got.values():
+        out = {k: recs[0][k] for k in ("shape", "M", "N", "K", "epi")}
+        for k in recs[0]:
+            if k.endswith("_us"):
+                out[k] = med([r[k] for r in recs])
+        spread = []
+        for a, b in (("chain_us", "chain_again_us"), ("w8_rule_us", "w8_again_us")):
+            v = [r[a] for r in recs] + [r[b] for r in recs]
+            spread.append(100.0 * (max(v) - min(v)) / min(v))
+        out["old_spread_pct"] = round(max(spread), 1)
+        out["gemm_int8_TOPS"] = round(2.0 * out["M"] * out["N"] * out["K"] / min(
+            v for k, v in out.items() if k.startswith("g_")) / 1e6, 1)
+        print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=0,
+                    help="--w8a8: run as this many child processes, print medians and spread")
+    ap.add_argument("--w8a8", action="store_true",
+                    help="--prefill: time the W8A8 path (--shape mt,nt,ks; --sweep: every one)")
     ap.add_argument("--prefill", type=int, nargs="+", default=None,
                     help="time the quantised prefill GEMM at these row counts (>= 65); "
                          "--shape mt,nt pins its launch shape, --sweep times every one")
@@ -255,7 +357,11 @@ def main():
     ap.add_argument("--shape", default=None, help="--rows: pin the launch shape, nt,ks")
     ap.add_argument("--sweep", action="store_true", help="--rows: every launch shape")
     args = ap.parse_args()
+    if args.prefill and args.w8a8 and args.rounds:
+        return rounds_prefill_i8(args)
     from fleetx_amd.ops import gemm as G
+    if args.prefill and args.w8a8:
+        return main_prefill_i8(args, G)
     if args.prefill:
         return main_prefill(args, G)
     if args.rows:

@@ -8,6 +8,10 @@ alternating, and prints one markdown row per (format, case): the medians over
 the rounds and the ratio on / off.
 
     python tools/bench_quant_prefill.py [--rounds 3] [--quant int8 int4_g256 mxfp4]
+    python tools/bench_quant_prefill.py --quant int8 --act
+
+``--act`` adds a third child per round, ``Generation.prefill_act_quant: int8``
+on top of the key (int8 only), and its columns.
 """
 import argparse
 import collections
@@ -30,8 +34,10 @@ def child(a):
                     max_position_embeddings=4096, hidden_dropout_prob=0.0,
                     attention_probs_dropout_prob=0.0, dtype=torch.bfloat16)
     model = GPTForPretraining(cfg).cuda().eval()
-    gen = G.GPTForGeneration(model, {"weight_quant": a.child,
-                                     "weight_quant_prefill": a.key == "on"}).eval()
+    conf = {"weight_quant": a.child, "weight_quant_prefill": a.key != "off"}
+    if a.key == "act":
+        conf["prefill_act_quant"] = "int8"
+    gen = G.GPTForGeneration(model, conf).eval()
     assert gen.requantize() is True
     dev = "cuda"
 
@@ -66,6 +72,8 @@ def main():
     ap.add_argument("--quant", nargs="+", default=["int8", "int4_g256", "mxfp4"])
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--act", action="store_true",
+                    help="also time prefill_act_quant: int8 on top of the key (int8 only)")
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--key", default="off", help=argparse.SUPPRESS)
     a = ap.parse_args()
@@ -74,7 +82,7 @@ def main():
     got = collections.defaultdict(list)
     for _ in range(a.rounds):
         for quant in a.quant:
-            for key in ("off", "on"):
+            for key in ("off", "on") + (("act",) if a.act and quant == "int8" else ()):
                 r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", quant,
                                     "--key", key, "--iters", str(a.iters)], capture_output=True,
                                    text=True, timeout=300)
@@ -92,6 +100,11 @@ def main():
             mo, mn = statistics.median(off), statistics.median(on)
             print("| %s | %s | %.2f (%.2f - %.2f) | %.2f (%.2f - %.2f) | %.2f |" % (
                 quant, case, mo, min(off), max(off), mn, min(on), max(on), mn / mo))
+            act = got.get((quant, case, "act"))
+            if act:
+                ma = statistics.median(act)
+                print("| %s + act int8 | %s | | %.2f (%.2f - %.2f) | %.2f |" % (
+                    quant, case, ma, min(act), max(act), ma / mo))
 
 
 if __name__ == "__main__":

@@ -137,8 +137,40 @@ def check_prefill_gemm():
     assert kernel == 4
 
 
+def check_prefill_gemm_i8():
+    """The x stage of ``csrc/kernels/prefill_gemm_i8.hip``: rows of 128 bytes
+    (eight 16-byte pieces of int8), lane (r, g) = (lane % 16, lane / 16) reads
+    ONE piece per 64-k step i, piece 4 i + g of row 16 mt + r, with
+    ``ds_read_b128``.  The 16-bit kernel's swizzle separates only the piece
+    pairs it reads; here the 8 lanes of a 16-lane service group whose rows share
+    a parity need 8 different slots, so every row pair gets its own XOR:
+    ``pi8_swz``: f = (row >> 1) & 7.  Checks it conflict-free, and the
+    kernel's closed forms of the two read addresses."""
+    def worst(f):
+        return max(cost_b128([128 * (l & 15) + 16 * ((4 * i + (l >> 4)) ^ f(l & 15))
+                              for l in range(64)]) for i in (0, 1))
+    print("prefill_gemm_i8 x stage naive:", worst(lambda r: 0), "cycles (ideal 4)")
+    print("pg_swz (the 16-bit kernel's):",
+          worst(lambda r: ((r >> 1) & 1) | (((r >> 2) & 1) << 2)), "cycles")
+    swz = lambda r: (r >> 1) & 7  # noqa: E731
+    kernel = worst(swz)
+    print("pi8_swz:", kernel, "cycles")
+    assert kernel == 4
+    for lane in range(64):
+        r, g = lane & 15, lane >> 4
+        xr0 = 128 * r + 16 * (g ^ swz(r))
+        assert [xr0, xr0 ^ 64] == [128 * r + 16 * ((4 * i + g) ^ swz(r)) for i in (0, 1)]
+    # the source side: lane l of stage piece p writes slot l % 8 of row 8 p + l / 8 and must
+    # fetch the piece that slot holds; every (row, piece) of a 128-row stage exactly once
+    seen = {(8 * p + (l >> 3), (l & 7) ^ swz(8 * p + (l >> 3))) for p in range(16) for l in range(64)}
+    assert len(seen) == 128 * 8
+
+
 if __name__ == "__main__":
     import sys
+    if "--prefill-gemm-i8" in sys.argv:
+        check_prefill_gemm_i8()
+        sys.exit(0)
     if "--check-frag" in sys.argv:
         check_frag()
         sys.exit(0)
