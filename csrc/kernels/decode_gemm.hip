@@ -1,7 +1,7 @@
 // Skinny GEMM for batched decoding: y[M, N] = x[M, K] W[N, K]^T, 17 <= M <= 64,
 // K % 1024 == 0, any N, 16-bit x and y, with the decoder layer's element-wise
 // work fused into the epilogue (GV_BIAS / GV_GELU / GV_RES / GV_QKV of
-// decode_gemv.h).  The twin of gemv_kernel for the rows it does not take: the
+// weight_operand.h).  The twin of gemv_kernel for the rows it does not take: the
 // step is still bound by the weight stream, so the weights are streamed once,
 // straight to VGPRs, and every weight operand is reused from registers by all
 // row tiles.  Weight operands: 16-bit, int8 with a scale per output row, int4
@@ -24,7 +24,7 @@
 //    32 int8 / 64 int4 weights per lane the two x register sets alone would
 //    take 128 / 256 VGPRs at MT = 4;
 //  * a quantised chunk becomes its two short8 A operands ONCE (cvt8 of
-//    decode_gemv.h; int4: the two-mask spread to 16 q first) and each feeds MT
+//    weight_operand.h; int4: the two-mask spread to 16 q first) and each feeds MT
 //    MFMAs v_mfma_f32_16x16x32, so the conversion is paid per weight, not per
 //    weight and row tile;
 //  * two register sets: chunk c + 1 is in flight under chunk c's MFMAs, in a
@@ -52,32 +52,20 @@
 // NT / MT do not enter, so the bits of an output row depend on that x row
 // alone, not on its index, on M or on the other rows.
 //
-// Built without packed fp32 VALU, as all new HIP code here (see flash_attn.hip,
-// FA_NO_PK32).  Resources and measurements: profiles/decode_rows/README.md.
-#include "decode_gemv.h"
+// Built without packed fp32 VALU, as all new HIP code here (FX_NO_PK32,
+// fx_common.h).  Resources and measurements: profiles/decode_rows/README.md.
 #include "fx_api.h"
+#include "weight_operand.h"
 
 namespace {
 
-#if defined(__HIP_DEVICE_COMPILE__)
-#define DG_NO_PK32 __attribute__((target("no-packed-fp32-ops"), flatten))
-#else
-#define DG_NO_PK32  // the host pass does not know the device feature
-#endif
-
 constexpr int DG_CHUNK = 64;  // k per chunk: 16 per lane, two MFMA k-steps
 
-typedef uint32_t uintx2 __attribute__((ext_vector_type(2)));
-
-// Weight operand policies: raw = a lane's 16 weights of one row and chunk as
-// loaded, ops() = their two MFMA A operands, PB = chunks per loop group, FMT =
-// the format's column of the launch table.
-struct G16 {
-  typedef uint16_t elt;
-  struct raw { short8 v[2]; };
-  static constexpr int PACK = 1, PB = 2, FMT = 0;
-  static constexpr bool SCALED = false, GROUPED = false, OPSCALED = false;
-  typedef float sc;
+// Weight operand policies (weight_operand.h) with what this kernel owns: PB =
+// chunks per loop group, FMT = the format's column of the launch table, load()
+// = a lane's raw of one row and chunk, streamed.
+struct G16 : Op16 {
+  static constexpr int PB = 2, FMT = 0;
   static __device__ __forceinline__ raw load(const elt* p) {
     const short8* q = reinterpret_cast<const short8*>(p);
     raw o;
@@ -85,64 +73,19 @@ struct G16 {
     o.v[1] = __builtin_nontemporal_load(q + 1);
     return o;
   }
-  template <typename T>
-  static __device__ __forceinline__ void ops(const raw& v, short8 (&a)[2]) {
-    a[0] = v.v[0];
-    a[1] = v.v[1];
-  }
 };
-
-struct G8 {
-  typedef int8_t elt;
-  typedef uintx4 raw;
-  static constexpr int PACK = 1, PB = 2, FMT = 1;
-  static constexpr bool SCALED = true, GROUPED = false, OPSCALED = false;
-  typedef float sc;
-  static __device__ __forceinline__ raw load(const elt* p) {
-    return __builtin_nontemporal_load(reinterpret_cast<const uintx4*>(p));
-  }
-  template <typename T>
-  static __device__ __forceinline__ void ops(const raw& v, short8 (&a)[2]) {
-    a[0] = cvt8<T>(v.x, v.y);
-    a[1] = cvt8<T>(v.z, v.w);
-  }
+struct G8 : Op8 {
+  static constexpr int PB = 2, FMT = 1;
+  static __device__ __forceinline__ raw load(const elt* p) { return load_w<raw, true>(p); }
 };
-
-struct G4 {
-  typedef uint8_t elt;
-  typedef uintx2 raw;
-  static constexpr int PACK = 2, PB = 4, FMT = 2;
-  static constexpr bool SCALED = false, GROUPED = true, OPSCALED = false;
-  typedef float sc;
-  static __device__ __forceinline__ raw load(const elt* p) {
-    return __builtin_nontemporal_load(reinterpret_cast<const uintx2*>(p));
-  }
-  // a dword is 8 weights: byte j = q[j] (low nibble), q[j + 4] (high nibble);
-  // two masks spread them to int8 operands holding 16 q (decode_gemv_w4.hip)
-  template <typename T>
-  static __device__ __forceinline__ void ops(const raw& v, short8 (&a)[2]) {
-    a[0] = cvt8<T>((v.x << 4) & 0xF0F0F0F0u, v.x & 0xF0F0F0F0u);
-    a[1] = cvt8<T>((v.y << 4) & 0xF0F0F0F0u, v.y & 0xF0F0F0F0u);
-  }
+struct G4 : Op4 {
+  static constexpr int PB = 4, FMT = 2;
+  static __device__ __forceinline__ raw load(const elt* p) { return load_w<raw, true>(p); }
 };
-
-// MXFP4 (decode_gemv_mx4.hip): a dword is 8 weights in k order, byte j = weights
-// 2j, 2j + 1; OPSCALED: ops() takes the fp32 scale of the lane's group.  It
-// shares int4's column of the launch table until its own sweep is taken.
-struct GM4 {
-  typedef uint8_t elt;
-  typedef uintx2 raw;
-  typedef uint8_t sc;
-  static constexpr int PACK = 2, PB = 4, FMT = 2;
-  static constexpr bool SCALED = false, GROUPED = false, OPSCALED = true;
-  static __device__ __forceinline__ raw load(const elt* p) {
-    return __builtin_nontemporal_load(reinterpret_cast<const uintx2*>(p));
-  }
-  template <typename T>
-  static __device__ __forceinline__ void ops(const raw& v, float s, short8 (&a)[2]) {
-    a[0] = mx4_cvt8<T>(v.x, s);
-    a[1] = mx4_cvt8<T>(v.y, s);
-  }
+// MXFP4 shares int4's column of the launch table until its own sweep is taken
+struct GM4 : OpM4 {
+  static constexpr int PB = 4, FMT = 2;
+  static __device__ __forceinline__ raw load(const elt* p) { return load_w<raw, true>(p); }
 };
 
 template <typename W>
@@ -164,51 +107,8 @@ struct GemmArgs {
   int vec;  // every epilogue operand admits 16-byte accesses at n % 8 == 0
 };
 
-// Epilogue of 8 consecutive columns n .. n + 7 (those < N) of row m: v holds
-// the summed accumulators.
-template <typename W, typename T>
-__device__ __forceinline__ void gemm_epilogue(const GemmArgs<W>& a, int m, int n, float (&v)[8]) {
-  const int cnt = min(8, a.N - n);
-  const bool full = a.vec && cnt == 8;
-  const int epi = a.epi;
-  float b[8], rs[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) b[j] = rs[j] = 0.f;
-  if (full) {
-    if (a.bias != nullptr) load8<T>(a.bias + n, b);
-    if (epi == GV_RES) load8<T>(a.res + (long)m * a.ldres + n, rs);
-  } else {
-    for (int j = 0; j < cnt; ++j) {
-      if (a.bias != nullptr) b[j] = Elt<T>::to_f(a.bias[n + j]);
-      if (epi == GV_RES) rs[j] = Elt<T>::to_f(a.res[(long)m * a.ldres + n + j]);
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    if constexpr (W::SCALED) v[j] *= a.scale[min(n + j, a.N - 1)];
-    if (a.bias != nullptr) v[j] += b[j];
-    if (epi == GV_GELU) v[j] = gelu_tanh(v[j]);
-    if (epi == GV_RES) v[j] += rs[j];
-  }
-  // where column c of row m goes
-  auto dst = [&](int c) -> uint16_t* {
-    if (epi != GV_QKV) return a.y + (long)m * a.ldy + c;
-    // packed [heads][3][head_dim] columns
-    const int D = a.head_dim;
-    const int h = c / (3 * D), tq = (c / D) % 3, d = c % D;
-    if (tq == 0) return a.y + (long)m * a.ldy + h * D + d;
-    const long cr = a.rows != nullptr ? a.rows[m] : m;
-    return (tq == 1 ? a.kc : a.vc) + ((cr * a.maxlen + a.pos[m]) * a.heads + h) * D + d;
-  };
-  if (full) {
-    store8<T>(dst(n), v);
-  } else {
-    for (int j = 0; j < cnt; ++j) *dst(n + j) = Elt<T>::from_f(v[j]);
-  }
-}
-
 template <typename W, typename T, int KS, int NT, int MT>
-__global__ __launch_bounds__(64 * KS) DG_NO_PK32 void decode_gemm_kernel(GemmArgs<W> a) {
+__global__ __launch_bounds__(64 * KS) FX_NO_PK32 void decode_gemm_kernel(GemmArgs<W> a) {
   __shared__ __attribute__((aligned(16))) float red[KS * MT * 256];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int r = lane & 15, g = lane >> 4;
@@ -358,7 +258,7 @@ __global__ __launch_bounds__(64 * KS) DG_NO_PK32 void decode_gemm_kernel(GemmArg
           v[4 + j] += p1[j];
         }
       }
-      gemm_epilogue<W, T>(a, m, n, v);
+      row_epilogue8<W, T, true>(a, m, n, v);
     }
   }
 }
@@ -396,8 +296,6 @@ bool gemm_launch(const GemmArgs<W>& a, int ks, int nt, int mt, hipStream_t s) {
   if (ks == 8) return gemm_launch_nt<W, T, 8>(a, nt, mt, s);
   return gemm_launch_nt<W, T, 4>(a, nt, mt, s);
 }
-
-inline bool al16(const void* p) { return (uintptr_t)p % 16 == 0; }
 
 // Launch table, filled from the sweep in profiles/decode_rows/ (medians of three
 // per figure): per measured (N, K) and format {16-bit, int8, int4; MXFP4 takes

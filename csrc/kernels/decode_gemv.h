@@ -33,27 +33,17 @@
 //   STEADY_LOOP   which of the kernel's two K-loop schedules runs
 //   PIN_KS / PIN_U / PIN_ROWS   environment variables that pin the launch
 //                 shape for tools/bench_gemv.py sweeps (nullptr: no such pin)
+// The epilogue codes GV_*, mma16 and the conversions the policies call (cvt8,
+// mx4_cvt8) are weight_operand.h's, shared with the kernels of the other row
+// counts.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 
-#include <type_traits>
-
-#include "fx_common.h"
+#include "weight_operand.h"
 
 namespace {
-
-typedef uint32_t uintx4 __attribute__((ext_vector_type(4)));
-
-//   GV_BIAS      y = acc + b                               (out-proj, LM head)
-//   GV_GELU      y = gelu_tanh(acc + b)                    (FFN1)
-//   GV_RES       y = acc + b + res                         (FFN2 + residual)
-//   GV_QKV       acc + b scattered to q[M, H, D] and the KV cache at this
-//                token's position (k/v_cache[M, maxlen, H, D])   (QKV + cache append);
-//                with a row map, row m goes to cache row rows[m] (several
-//                consecutive tokens of one sample in one call)
-enum { GV_BIAS = 0, GV_GELU = 1, GV_RES = 2, GV_QKV = 3 };
 
 template <typename W>
 struct GemvArgs {
@@ -75,68 +65,6 @@ struct GemvArgs {
   const uint16_t* ln_b;
   float ln_eps;
 };
-
-template <typename T>
-__device__ __forceinline__ floatx4 mma16(const short8& a, const short8& b, const floatx4& c) {
-  if constexpr (std::is_same<T, bf16>::value)
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a),
-                                                   __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a),
-                                                  __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
-// int8 weight operands (W8; W4 after it has spread its nibbles into bytes)
-// two int8 (bytes B0 and B1 of v) -> two packed 16-bit floats.  Every integer
-// in [-128, 127] is exact in bf16 (8 significant bits) and fp16.
-template <typename T, int B0, int B1>
-__device__ __forceinline__ uint32_t cvt2(uint32_t v) {
-  const float f0 = (float)(int8_t)(v >> (8 * B0));
-  const float f1 = (float)(int8_t)(v >> (8 * B1));
-  if constexpr (std::is_same<T, bf16>::value) {
-    // an exact small integer: the low 16 fp32 bits are zero, truncation is exact
-    return __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, f1),
-                                 __builtin_bit_cast(uint32_t, f0), 0x07060302u);
-  } else {
-    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(f0, f1));
-  }
-}
-// eight int8 (two dwords) -> one MFMA operand, element order = byte order
-template <typename T>
-__device__ __forceinline__ short8 cvt8(uint32_t lo, uint32_t hi) {
-  uint4 o;
-  o.x = cvt2<T, 0, 1>(lo);
-  o.y = cvt2<T, 2, 3>(lo);
-  o.z = cvt2<T, 0, 1>(hi);
-  o.w = cvt2<T, 2, 3>(hi);
-  return __builtin_bit_cast(short8, o);
-}
-
-// MXFP4 weight operands (WMX4; GM4 of decode_gemm.hip)
-// an e8m0 scale byte (the low byte of v; 1..254) -> the fp32 2^(e - 127)
-__device__ __forceinline__ float mx4_scale(uint32_t v) {
-  return __builtin_bit_cast(float, (v & 0xFFu) << 23);
-}
-// eight e2m1 (one dword: byte j = elements 2j, 2j + 1 in its low, high nibble)
-// times scale -> one MFMA operand in element order: v_cvt_scalef32_pk_*_fp4,
-// one instruction per byte.  Exact: a code times a power of two is a 16-bit
-// float (fp16: while it is a normal one).
-template <typename T>
-__device__ __forceinline__ short8 mx4_cvt8(uint32_t v, float scale) {
-  uint4 o;
-  if constexpr (std::is_same<T, bf16>::value) {
-    o.x = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, scale, 0));
-    o.y = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, scale, 1));
-    o.z = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, scale, 2));
-    o.w = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, scale, 3));
-  } else {
-    o.x = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(v, scale, 0));
-    o.y = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(v, scale, 1));
-    o.z = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(v, scale, 2));
-    o.w = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(v, scale, 3));
-  }
-  return __builtin_bit_cast(short8, o);
-}
 
 template <typename W, int U>
 __device__ __forceinline__ void load_w(typename W::reg (&wv)[U][2], const typename W::elt* wp,

@@ -44,8 +44,8 @@
 // FLEETX_GEMV_MX4_KS (4 / 8 waves) and FLEETX_GEMV_MX4_ROWS (8 / 16 columns per
 // block) pin the launch shape for tools/bench_gemv.py --mx4 sweeps.
 //
-// Built without packed fp32 VALU, as all new HIP code here (see flash_attn.hip,
-// FA_NO_PK32).  The kernel is the shared header's, so the attribute is applied
+// Built without packed fp32 VALU, as all new HIP code here (FX_NO_PK32,
+// fx_common.h).  The kernel is the shared header's, so the attribute is applied
 // to every function of this file's device pass instead of to the kernel, with
 // flatten, so that the runtime's header functions still inline.
 #include <hip/hip_runtime.h>

@@ -13,7 +13,7 @@
 // one dword per MFMA k-step, and a dword becomes its operand with two masks:
 //   (v << 4) & 0xF0F0F0F0   bytes = 16 * q[8i + 0..3]   (int8, exact)
 //    v       & 0xF0F0F0F0   bytes = 16 * q[8i + 4..7]
-// which are int8 operands for the W8 conversion (cvt8 in decode_gemv.h).  The
+// which are int8 operands for the W8 conversion (cvt8 in weight_operand.h).  The
 // factor 16 is exact in bf16 and fp16 (|16 q| <= 128) and leaves with the
 // scale: the chunk sum is multiplied by scale / 16.
 //

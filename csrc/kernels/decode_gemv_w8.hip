@@ -7,7 +7,7 @@
 // file is the int8 weight operand, converted in registers:
 //  * per 128-k chunk every lane loads 32 contiguous bytes of one q row and the
 //    matching 32 x elements, for the chunk's four MFMA k-steps;
-//  * each int8 is sign-extended and converted to fp32 (cvt8 in decode_gemv.h,
+//  * each int8 is sign-extended and converted to fp32 (cvt8 in weight_operand.h,
 //    shared with the int4 operand), then packed to the
 //    activation dtype (bf16: the upper half of the fp32, exact for |q| <= 127;
 //    fp16: cvt_pkrtz, exact too) right before its MFMA -- ~1.5 VALU lane-ops

@@ -374,11 +374,6 @@ __device__ __forceinline__ void key_bias_add(floatx16 (&acc)[2], const float* kb
   key_bias_add1(acc[1], kb + 32, h, sl2);
 }
 
-__device__ __forceinline__ int xcd_remap(int bid, int nblk) {
-  const int xcd = bid & 7, pos = bid >> 3, q = nblk >> 3, r = nblk & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-}
-
 // Causal work order (longest-processing-time first).  A causal block's cost
 // grows with its distance from the diagonal, so dispatching (head, block) in
 // head-major order leaves the heaviest blocks of the LAST heads to start near
@@ -917,12 +912,12 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void fa_fwd_qoff_kernel(AttnParams
 // one's time over 88 cases, profiles/prefill_split/).  `flatten` goes with
 // it: a callee that is merely `inline` (the HIP headers' __shfl_xor,
 // __syncthreads, make_float4) is otherwise kept out of line, because its
-// target features differ from the kernel's.
+// target features differ from the kernel's.  The attribute is FX_NO_PK32
+// (fx_common.h).
 // ============================================================================
-#define FA_NO_PK32 __attribute__((target("no-packed-fp32-ops"), flatten))
 
 template <typename T, int D, int NW>
-__global__ __launch_bounds__(64 * NW, 8 / NW) FA_NO_PK32 void fa_fwd_qoff_split_kernel(
+__global__ __launch_bounds__(64 * NW, 8 / NW) FX_NO_PK32 void fa_fwd_qoff_split_kernel(
     AttnParams P, const int* q_starts, float* ws_o, float* ws_ml, int nsplit, int min_tiles) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int KV = 64, TB = KV * D * 2, QB = 32 * NW;
@@ -1029,7 +1024,7 @@ __device__ __forceinline__ uint32_t pack16(float lo, float hi) {  // two rounded
   return (uint32_t)Elt<T>::from_f(lo) | ((uint32_t)Elt<T>::from_f(hi) << 16);
 }
 template <typename T>
-__global__ __launch_bounds__(256) FA_NO_PK32 void fa_split_combine_kernel(
+__global__ __launch_bounds__(256) FX_NO_PK32 void fa_split_combine_kernel(
     const float* ws_o, const float* ws_ml, uint16_t* out, float* lse, long so_b, long so_s,
     long so_h, int H, int Sq, int Dt, int dval, int nsplit, long nrows, int row16) {
   const int lpr = Dt / 8, rpw = 256 / lpr;

@@ -134,6 +134,26 @@ __device__ __forceinline__ float gelu_erf_grad(float x) {
          x * 0.3989422804014327f * __expf(-0.5f * x * x);
 }
 
+// ---------------------------------------------------------------- kernels
+// Kernel attribute: built without packed fp32 VALU (v_pk_fma_f32 and kin), as
+// all new HIP code of this project is; flash_attn.hip (fa_fwd_qoff_split_kernel)
+// has the reason, and why `flatten` goes with it.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define FX_NO_PK32 __attribute__((target("no-packed-fp32-ops"), flatten))
+#else
+#define FX_NO_PK32  // the host pass does not know the device feature
+#endif
+
+// Block id -> logical id, so that consecutive logical ids run on one XCD:
+// hardware block b goes to XCD b % 8, and XCD x gets a contiguous range of ids.
+__device__ __forceinline__ int xcd_remap(int bid, int nblk) {
+  const int xcd = bid & 7, pos = bid >> 3, q = nblk >> 3, r = nblk & 7;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
+}
+
 #define FX_CHECK_LAUNCH() (void)hipGetLastError()
 
 static inline int fx_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// host: p admits 16-byte accesses (nullptr does)
+static inline bool al16(const void* p) { return (uintptr_t)p % 16 == 0; }

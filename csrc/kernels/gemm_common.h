@@ -63,11 +63,6 @@ struct GemmParams {
   int ctr;
 };
 
-__device__ __forceinline__ int xcd_remap(int bid, int nblk) {
-  const int xcd = bid & 7, pos = bid >> 3, q = nblk >> 3, r = nblk & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-}
-
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* p, long bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
 }

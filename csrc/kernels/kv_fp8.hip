@@ -15,19 +15,13 @@
 // partials (fx_decode_attn_combine), with a lane map of its own: 16 elements
 // of a key row per lane instead of 8.
 //
-// Built without packed fp32 VALU, as all new HIP code here (see flash_attn.hip,
-// FA_NO_PK32).  Plain vector stores, no atomics.  Resources and measurements:
+// Built without packed fp32 VALU, as all new HIP code here (FX_NO_PK32,
+// fx_common.h).  Plain vector stores, no atomics.  Resources and measurements:
 // profiles/kv_fp8/README.md.
 #include "fx_api.h"
 #include "fx_common.h"
 
 namespace {
-
-#if defined(__HIP_DEVICE_COMPILE__)
-#define KV_NO_PK32 __attribute__((target("no-packed-fp32-ops"), flatten))
-#else
-#define KV_NO_PK32  // the host pass does not know the device feature
-#endif
 
 typedef float kv_float2 __attribute__((ext_vector_type(2)));
 
@@ -69,7 +63,7 @@ __device__ __forceinline__ uint4 pack16_fp8(const float* f) {
 // so a captured launch follows it.  A thread converts 16 elements of K and of
 // V: two 16-byte loads and one 16-byte store each, tpr = H*D/16 threads a row.
 template <typename T>
-__global__ __launch_bounds__(256) KV_NO_PK32 void kv_append_fp8_kernel(
+__global__ __launch_bounds__(256) FX_NO_PK32 void kv_append_fp8_kernel(
     const uint16_t* __restrict__ k_src, const uint16_t* __restrict__ v_src, long ssr, long ssh,
     int S, const int* __restrict__ pos, uint8_t* __restrict__ k_cache,
     uint8_t* __restrict__ v_cache, long scb, long scs, long sch, int maxlen, int D, int tpr,
@@ -131,7 +125,7 @@ __device__ __forceinline__ void merge_state16(float& m, float& l, float* o, floa
 // and one memory round trip.  Out-of-range lanes load the split's first row,
 // so no row at or past lens[b] is ever read; lens[b] == 0 gives zeros.
 template <typename T, int D, int NW>
-__global__ __launch_bounds__(64 * NW) KV_NO_PK32 void decode_attn_fp8_kernel(
+__global__ __launch_bounds__(64 * NW) FX_NO_PK32 void decode_attn_fp8_kernel(
     const uint16_t* __restrict__ q, const uint8_t* __restrict__ kc,
     const uint8_t* __restrict__ vc, const int* __restrict__ lens, float* __restrict__ ws, int H,
     int nsplit, int chunk, int maxlen, long sqb, long sqh, long skb, long sks, long skh,
@@ -255,8 +249,6 @@ __global__ __launch_bounds__(64 * NW) KV_NO_PK32 void decode_attn_fp8_kernel(
     }
   }
 }
-
-inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 

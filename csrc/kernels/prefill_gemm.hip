@@ -1,7 +1,7 @@
 // Weight-only quantised prefill GEMM: y[M, N] = x[M, K] dequant(W[N, K])^T,
 // M >= 65, K % 1024 == 0, any N, 16-bit x and y (bf16 / fp16), fp32
 // accumulation, with the decoder layer's element-wise work fused into the
-// epilogue (GV_BIAS / GV_GELU / GV_RES of decode_gemv.h; no GV_QKV scatter).
+// epilogue (GV_BIAS / GV_GELU / GV_RES of weight_operand.h; no GV_QKV scatter).
 // The sibling of gemv_kernel (1..16 rows) and decode_gemm_kernel (17..64 rows)
 // for the rows they do not take, on the SAME packed copies -- nothing is
 // repacked: int8 q[N, K] with an fp32 scale [N]; int4 nibbles as pack_int4
@@ -61,75 +61,22 @@
 // decode_gemm_kernel give the same row: those split K over their waves and sum
 // the wave partials afterwards.
 //
-// Built without packed fp32 VALU, as all new HIP code here (see flash_attn.hip,
-// FA_NO_PK32).  Resources and measurements: profiles/quant_prefill/README.md.
-#include "decode_gemv.h"
+// Built without packed fp32 VALU, as all new HIP code here (FX_NO_PK32,
+// fx_common.h).  Resources and measurements: profiles/quant_prefill/README.md.
 #include "fx_api.h"
+#include "weight_operand.h"
 
 namespace {
-
-#if defined(__HIP_DEVICE_COMPILE__)
-#define PG_NO_PK32 __attribute__((target("no-packed-fp32-ops"), flatten))
-#else
-#define PG_NO_PK32  // the host pass does not know the device feature
-#endif
 
 constexpr int PG_CHUNK = 64;  // k per chunk: 16 per lane, two MFMA k-steps
 constexpr int PG_PB = 4;      // chunks per loop group: 256 k, one int4 scale group
 
-typedef uint32_t uintx2 __attribute__((ext_vector_type(2)));
-
-// Weight operand policies (G8 / G4 / GM4 of decode_gemm.hip with the choice of
-// a streaming load): raw = a lane's 16 weights of one row and chunk as loaded,
-// ops() = their two MFMA A operands.
-struct P8 {
-  typedef int8_t elt;
-  typedef uintx4 raw;
-  typedef float sc;
-  static constexpr int PACK = 1;
-  static constexpr bool SCALED = true, GROUPED = false, OPSCALED = false;
-  template <typename T>
-  static __device__ __forceinline__ void ops(const raw& v, short8 (&a)[2]) {
-    a[0] = cvt8<T>(v.x, v.y);
-    a[1] = cvt8<T>(v.z, v.w);
-  }
-};
-
-struct P4 {
-  typedef uint8_t elt;
-  typedef uintx2 raw;
-  typedef float sc;
-  static constexpr int PACK = 2;
-  static constexpr bool SCALED = false, GROUPED = true, OPSCALED = false;
-  // a dword is 8 weights: byte j = q[j] (low nibble), q[j + 4] (high nibble);
-  // two masks spread them to int8 operands holding 16 q (decode_gemv_w4.hip)
-  template <typename T>
-  static __device__ __forceinline__ void ops(const raw& v, short8 (&a)[2]) {
-    a[0] = cvt8<T>((v.x << 4) & 0xF0F0F0F0u, v.x & 0xF0F0F0F0u);
-    a[1] = cvt8<T>((v.y << 4) & 0xF0F0F0F0u, v.y & 0xF0F0F0F0u);
-  }
-};
-
-struct PM4 {
-  typedef uint8_t elt;
-  typedef uintx2 raw;
-  typedef uint8_t sc;
-  static constexpr int PACK = 2;
-  static constexpr bool SCALED = false, GROUPED = false, OPSCALED = true;
-  // a dword is 8 weights in k order; s: the fp32 scale of the lane's group
-  template <typename T>
-  static __device__ __forceinline__ void ops(const raw& v, float s, short8 (&a)[2]) {
-    a[0] = mx4_cvt8<T>(v.x, s);
-    a[1] = mx4_cvt8<T>(v.y, s);
-  }
-};
-
-// ST: the panel is read once (one row block) -> streaming load
-template <typename R, bool ST>
-__device__ __forceinline__ R pg_load_w(const void* p) {
-  if constexpr (ST) return __builtin_nontemporal_load(reinterpret_cast<const R*>(p));
-  else return *reinterpret_cast<const R*>(p);
-}
+// Weight operand policies (weight_operand.h); the kernel chooses the load: the
+// panel is streamed (load_w<raw, true>) only while it is read once, by one row
+// block.  The names are this kernel's template arguments.
+struct P8 : Op8 {};
+struct P4 : Op4 {};
+struct PM4 : OpM4 {};
 
 template <typename W>
 struct PrefillArgs {
@@ -145,52 +92,11 @@ struct PrefillArgs {
   int vec;  // every epilogue operand admits 16-byte accesses at n % 8 == 0
 };
 
-// the contiguous range of ids an XCD gets (gemm_common.h, flash_attn.hip)
-__device__ __forceinline__ int pg_xcd_remap(int bid, int nblk) {
-  const int xcd = bid & 7, pos = bid >> 3, q = nblk >> 3, r = nblk & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-}
-
 // bank swizzle of the x stage: 16-byte slot s of row m holds piece s ^ pg_swz(m)
 __device__ __forceinline__ int pg_swz(int m) { return ((m >> 1) & 1) | (((m >> 2) & 1) << 2); }
 
-// Epilogue of 8 consecutive columns n .. n + 7 (those < N) of row m: v holds
-// the accumulators.  Row scale, bias, GeLU or residual, one rounding.
-template <typename W, typename T>
-__device__ __forceinline__ void prefill_epilogue(const PrefillArgs<W>& a, int m, int n,
-                                                 float (&v)[8]) {
-  const int cnt = min(8, a.N - n);
-  const bool full = a.vec && cnt == 8;
-  const int epi = a.epi;
-  float b[8], rs[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) b[j] = rs[j] = 0.f;
-  if (full) {
-    if (a.bias != nullptr) load8<T>(a.bias + n, b);
-    if (epi == GV_RES) load8<T>(a.res + (long)m * a.ldres + n, rs);
-  } else {
-    for (int j = 0; j < cnt; ++j) {
-      if (a.bias != nullptr) b[j] = Elt<T>::to_f(a.bias[n + j]);
-      if (epi == GV_RES) rs[j] = Elt<T>::to_f(a.res[(long)m * a.ldres + n + j]);
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    if constexpr (W::SCALED) v[j] *= a.scale[min(n + j, a.N - 1)];
-    if (a.bias != nullptr) v[j] += b[j];
-    if (epi == GV_GELU) v[j] = gelu_tanh(v[j]);
-    if (epi == GV_RES) v[j] += rs[j];
-  }
-  uint16_t* dst = a.y + (long)m * a.ldy + n;
-  if (full) {
-    store8<T>(dst, v);
-  } else {
-    for (int j = 0; j < cnt; ++j) dst[j] = Elt<T>::from_f(v[j]);
-  }
-}
-
 template <typename W, typename T, int MT, int NT, bool ST>
-__global__ __launch_bounds__(256) PG_NO_PK32 void prefill_gemm_kernel(PrefillArgs<W> a) {
+__global__ __launch_bounds__(256) FX_NO_PK32 void prefill_gemm_kernel(PrefillArgs<W> a) {
   constexpr int BM = 16 * MT;
   constexpr int STAGE = BM * 2 * PG_CHUNK;  // bytes of one x stage: BM rows of 128 bytes
   constexpr int NI = BM / 32;               // global_load_lds instructions per wave and chunk
@@ -198,7 +104,7 @@ __global__ __launch_bounds__(256) PG_NO_PK32 void prefill_gemm_kernel(PrefillArg
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int r = lane & 15, g = lane >> 4;
   // consecutive ids = the row blocks of one weight panel
-  const int lid = pg_xcd_remap(blockIdx.x, gridDim.x);
+  const int lid = xcd_remap(blockIdx.x, gridDim.x);
   const int m0 = (lid % a.nbm) * BM;
   const int n0 = (lid / a.nbm) * (64 * NT) + 16 * NT * w;
   const typename W::elt* wp[NT];
@@ -244,7 +150,7 @@ __global__ __launch_bounds__(256) PG_NO_PK32 void prefill_gemm_kernel(PrefillArg
 #define PG_LOAD(S, c)                                                            \
   do {                                                                           \
     _Pragma("unroll") for (int nt = 0; nt < NT; ++nt)                            \
-        wv[S][nt] = pg_load_w<typename W::raw, ST>(wp[nt] + (long)(c) * (PG_CHUNK / W::PACK)); \
+        wv[S][nt] = load_w<typename W::raw, ST>(wp[nt] + (long)(c) * (PG_CHUNK / W::PACK)); \
     _Pragma("unroll") for (int u = 0; u < NI; ++u)                               \
         __builtin_amdgcn_global_load_lds(                                        \
             (const void*)(xs[u] + (long)(c) * PG_CHUNK),                         \
@@ -352,7 +258,7 @@ __global__ __launch_bounds__(256) PG_NO_PK32 void prefill_gemm_kernel(PrefillArg
           v[j] = p0[j];
           v[4 + j] = p1[j];
         }
-        prefill_epilogue<W, T>(a, m, n, v);
+        row_epilogue8<W, T, false>(a, m, n, v);
       }
     }
   }
@@ -390,8 +296,6 @@ bool prefill_launch(const PrefillArgs<W>& a, int mt, int nt, hipStream_t s) {
   return prefill_launch_nt<W, T, 8>(a, nt, s);
 }
 
-inline bool pg_al16(const void* p) { return (uintptr_t)p % 16 == 0; }
-
 // Launch shape from (M, N) and the format, from the sweep in
 // profiles/quant_prefill/README.md (the four layer shapes of 1.3B and 6.7B and
 // the LM head at 65 / 128 / 512 / 2048 rows, every tile, weights streamed from
@@ -426,8 +330,8 @@ int prefill_gemm_entry(int dt, int epi, int M, int N, int K, const void* x, long
                        const void* res, long ldres, void* y, long ldy, int mt, int nt,
                        hipStream_t s) {
   if (M < 65 || N < 1 || K < 1024 || K % 1024 != 0 || (ldx % 8) ||
-      (ldw * sizeof(typename W::elt) % 16) || !pg_al16(x) || !pg_al16(w) || y == nullptr ||
-      scale == nullptr || (W::OPSCALED && !pg_al16(scale)))
+      (ldw * sizeof(typename W::elt) % 16) || !al16(x) || !al16(w) || y == nullptr ||
+      scale == nullptr || (W::OPSCALED && !al16(scale)))
     return 0;
   if (epi < GV_BIAS || epi > GV_RES) return 0;
   if (epi == GV_RES && res == nullptr) return 0;
@@ -442,8 +346,8 @@ int prefill_gemm_entry(int dt, int epi, int M, int N, int K, const void* x, long
   a.ldx = ldx; a.ldw = ldw; a.ldy = ldy; a.ldres = ldres;
   a.M = M; a.N = N; a.K = K; a.epi = epi;
   a.nbm = (M + 16 * mt - 1) / (16 * mt);
-  a.vec = pg_al16(y) && ldy % 8 == 0 && pg_al16(bias) &&
-          (epi != GV_RES || (pg_al16(res) && ldres % 8 == 0));
+  a.vec = al16(y) && ldy % 8 == 0 && al16(bias) &&
+          (epi != GV_RES || (al16(res) && ldres % 8 == 0));
   const bool ok = dt == 0 ? prefill_launch<W, bf16>(a, mt, nt, s)
                           : prefill_launch<W, f16>(a, mt, nt, s);
   if (!ok) return 0;

@@ -9,7 +9,7 @@
 // M >= 65, K % 1024 == 0, K <= 65536 (K * 127 * 127 < 2^31: the int32 sum
 // cannot overflow), any N; wq [N, K] / sw [N] are what quantize_weight_int8
 // makes and decode_linear_w8 / prefill_gemm_w8 read, nothing is repacked; y is
-// 16-bit; the epilogues are GV_BIAS / GV_GELU / GV_RES of decode_gemv.h.
+// 16-bit; the epilogues are GV_BIAS / GV_GELU / GV_RES of weight_operand.h.
 //
 // Row quantiser.  amax = max_k |float(x[m, k])|, sx = amax > 0 ? amax / 127 : 1
 // (an IEEE division), xq = clamp(rintf(float(x) / sx), -127, 127), ties to
@@ -61,19 +61,12 @@
 //
 // Built without packed fp32 VALU, as all new HIP code here.  Resources and
 // measurements: profiles/prefill_w8a8/README.md.
-#include "decode_gemv.h"
 #include "fx_api.h"
+#include "weight_operand.h"
 
 namespace {
 
-#if defined(__HIP_DEVICE_COMPILE__)
-#define PI8_NO_PK32 __attribute__((target("no-packed-fp32-ops"), flatten))
-#else
-#define PI8_NO_PK32  // the host pass does not know the device feature
-#endif
-
 typedef int intx4 __attribute__((ext_vector_type(4)));
-typedef uint32_t uintx2 __attribute__((ext_vector_type(2)));
 
 constexpr int PI8_CHUNK = 128;  // k per chunk and bytes per stage row: two 64-k MFMA steps
 
@@ -83,7 +76,7 @@ constexpr int PI8_CHUNK = 128;  // k per chunk and bytes per stage row: two 64-k
 // NTH threads on one row, V 16-byte vectors (8 elements) per thread, vector c =
 // threadIdx.x + NTH v; NTH * V * 8 >= K (host).
 template <typename T, int NTH, int V>
-__global__ __launch_bounds__(NTH) PI8_NO_PK32 void quant_rows_i8_kernel(
+__global__ __launch_bounds__(NTH) FX_NO_PK32 void quant_rows_i8_kernel(
     const uint16_t* __restrict__ x, long ldx, int8_t* __restrict__ xq, float* __restrict__ sx,
     int K) {
   __shared__ float part[NTH / 64];
@@ -165,12 +158,6 @@ struct PI8Args {
   int vec;  // every epilogue operand admits 16-byte accesses at n % 8 == 0
 };
 
-// the contiguous range of ids an XCD gets (prefill_gemm.hip)
-__device__ __forceinline__ int pi8_xcd_remap(int bid, int nblk) {
-  const int xcd = bid & 7, pos = bid >> 3, q = nblk >> 3, r = nblk & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-}
-
 // bank swizzle of the x stage: 16-byte slot s of row m holds piece s ^ pi8_swz(m)
 __device__ __forceinline__ int pi8_swz(int m) { return (m >> 1) & 7; }
 
@@ -184,17 +171,7 @@ __device__ __forceinline__ void pi8_epilogue(const PI8Args& a, int m, int n, con
   const bool full = a.vec && cnt == 8;
   const int epi = a.epi;
   float b[8], rs[8], v[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) b[j] = rs[j] = 0.f;
-  if (full) {
-    if (a.bias != nullptr) load8<T>(a.bias + n, b);
-    if (epi == GV_RES) load8<T>(a.res + (long)m * a.ldres + n, rs);
-  } else {
-    for (int j = 0; j < cnt; ++j) {
-      if (a.bias != nullptr) b[j] = Elt<T>::to_f(a.bias[n + j]);
-      if (epi == GV_RES) rs[j] = Elt<T>::to_f(a.res[(long)m * a.ldres + n + j]);
-    }
-  }
+  EPI8_LOAD(b, rs);
   const float sxm = a.sx[m];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
@@ -204,17 +181,12 @@ __device__ __forceinline__ void pi8_epilogue(const PI8Args& a, int m, int n, con
     if (epi == GV_GELU) v[j] = gelu_tanh(v[j]);
     if (epi == GV_RES) v[j] = v[j] + rs[j];
   }
-  uint16_t* dst = a.y + (long)m * a.ldy + n;
-  if (full) {
-    store8<T>(dst, v);
-  } else {
-    for (int j = 0; j < cnt; ++j) dst[j] = Elt<T>::from_f(v[j]);
-  }
+  EPI8_STORE(v);
 }
 
 // SPLIT: the block stores its int32 partial to its slab (T is not used)
 template <typename T, int MT, int NT, bool SPLIT>
-__global__ __launch_bounds__(256) PI8_NO_PK32 void prefill_gemm_i8_kernel(PI8Args a) {
+__global__ __launch_bounds__(256) FX_NO_PK32 void prefill_gemm_i8_kernel(PI8Args a) {
   constexpr int BM = 16 * MT;
   constexpr int STAGE = BM * PI8_CHUNK;  // bytes of one x stage: BM rows of 128 bytes
   constexpr int NI = BM / 32;            // global_load_lds instructions per wave and chunk
@@ -222,7 +194,7 @@ __global__ __launch_bounds__(256) PI8_NO_PK32 void prefill_gemm_i8_kernel(PI8Arg
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int r = lane & 15, g = lane >> 4;
   // consecutive ids = the row blocks of one (weight panel, K split)
-  const int lid = pi8_xcd_remap(blockIdx.x, gridDim.x);
+  const int lid = xcd_remap(blockIdx.x, gridDim.x);
   const int m0 = (lid % a.nbm) * BM;
   const int rest = lid / a.nbm;
   const int split = rest % a.ks;
@@ -335,7 +307,7 @@ __global__ __launch_bounds__(256) PI8_NO_PK32 void prefill_gemm_i8_kernel(PI8Arg
 
 // one thread per (row, 8 columns): the int32 sum of the KS slabs, the epilogue
 template <typename T>
-__global__ __launch_bounds__(256) PI8_NO_PK32 void prefill_i8_finish_kernel(PI8Args a) {
+__global__ __launch_bounds__(256) FX_NO_PK32 void prefill_i8_finish_kernel(PI8Args a) {
   const int noct = (int)(a.ldp / 8);
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= (long)a.M * noct) return;
@@ -380,8 +352,6 @@ void pi8_launch(const PI8Args& a, int mt, int nt, hipStream_t s) {
   pi8_launch_nt<T, 8>(a, nt, s);
 }
 
-inline bool pi8_al16(const void* p) { return (uintptr_t)p % 16 == 0; }
-
 // Launch shape from (M, N, K), from the sweep in profiles/prefill_w8a8/README.md
 // (the four layer shapes of 1.3B and 6.7B and the LM head at 65 / 128 / 512 /
 // 2048 rows, every tile and split, weights streamed from HBM; medians of three
@@ -415,8 +385,8 @@ void prefill_i8_rule(int M, int N, int K, int& mt, int& nt, int& ks) {
 // covered: K % 1024 != 0, K > 65536, rows that do not admit 16-byte loads.
 extern "C" int fx_quant_rows_i8(int dt, int M, int K, const void* x, long ldx, int8_t* xq,
                                 float* sx, hipStream_t s) {
-  if (M < 1 || K < 1024 || K % 1024 != 0 || K > 65536 || ldx % 8 || ldx < K || !pi8_al16(x) ||
-      !pi8_al16(xq) || xq == nullptr || sx == nullptr)
+  if (M < 1 || K < 1024 || K % 1024 != 0 || K > 65536 || ldx % 8 || ldx < K || !al16(x) ||
+      !al16(xq) || xq == nullptr || sx == nullptr)
     return 0;
   if (dt == 0) quant_rows_launch<bf16>(x, ldx, xq, sx, M, K, s);
   else quant_rows_launch<f16>(x, ldx, xq, sx, M, K, s);
@@ -441,7 +411,7 @@ extern "C" int fx_prefill_gemm_w8a8(int dt, int epi, int M, int N, int K, const 
                                     long ldres, void* y, long ldy, int* slab, long slab_elems,
                                     int mt, int nt, int ks, hipStream_t s) {
   if (M < 65 || N < 1 || K < 1024 || K % 1024 != 0 || K > 65536 || ldx % 16 || ldw % 16 ||
-      ldx < K || ldw < K || !pi8_al16(xq) || !pi8_al16(wq) || xq == nullptr || wq == nullptr ||
+      ldx < K || ldw < K || !al16(xq) || !al16(wq) || xq == nullptr || wq == nullptr ||
       y == nullptr || sx == nullptr || wscale == nullptr)
     return 0;
   if (epi < GV_BIAS || epi > GV_RES) return 0;
@@ -460,10 +430,10 @@ extern "C" int fx_prefill_gemm_w8a8(int dt, int epi, int M, int N, int K, const 
   a.M = M; a.N = N; a.K = K; a.epi = epi;
   a.nbm = (M + 16 * mt - 1) / (16 * mt);
   a.ks = ks;
-  if (ks > 1 && (slab == nullptr || !pi8_al16(slab) || slab_elems < (long)ks * M * a.ldp))
+  if (ks > 1 && (slab == nullptr || !al16(slab) || slab_elems < (long)ks * M * a.ldp))
     return 0;
-  a.vec = pi8_al16(y) && ldy % 8 == 0 && pi8_al16(bias) &&
-          (epi != GV_RES || (pi8_al16(res) && ldres % 8 == 0));
+  a.vec = al16(y) && ldy % 8 == 0 && al16(bias) &&
+          (epi != GV_RES || (al16(res) && ldres % 8 == 0));
   if (dt == 0) pi8_launch<bf16>(a, mt, nt, s);
   else pi8_launch<f16>(a, mt, nt, s);
   return ((N + 64 * nt - 1) / (64 * nt)) * ks * a.nbm;

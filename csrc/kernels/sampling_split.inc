@@ -51,12 +51,6 @@
 
 namespace {
 
-#if defined(__HIP_DEVICE_COMPILE__)
-#define SS_NO_PK32 __attribute__((target("no-packed-fp32-ops"), flatten))
-#else
-#define SS_NO_PK32  // the host pass does not know the device feature
-#endif
-
 constexpr int PT = 256;                 // part kernel: threads
 constexpr int PE = 8;                   // logits per thread
 constexpr int SLICE = PT * PE;          // vocabulary indices per slice
@@ -235,7 +229,7 @@ __device__ __forceinline__ void split_part(const L& load, int V, int slice, floa
 }
 
 template <typename T>
-__global__ __launch_bounds__(PT) SS_NO_PK32 void sample_part_kernel(
+__global__ __launch_bounds__(PT) FX_NO_PK32 void sample_part_kernel(
     const T* __restrict__ logits, long ld_row, int V, int G, float inv_temp, int top_k,
     float* __restrict__ ws) {
   __shared__ PartShared q;
@@ -259,7 +253,7 @@ __device__ __forceinline__ ProcLoad select_load(const SelectArgs& a, int row, in
   return load;
 }
 
-__global__ __launch_bounds__(PT) SS_NO_PK32 void select_part_kernel(SelectArgs a, int G,
+__global__ __launch_bounds__(PT) FX_NO_PK32 void select_part_kernel(SelectArgs a, int G,
                                                                     float* __restrict__ ws) {
   __shared__ PartShared q;
   const int row = blockIdx.x / G, slice = blockIdx.x - row * G;
@@ -462,7 +456,7 @@ __device__ __forceinline__ int split_finish(const L& load, const float* __restri
 }
 
 template <typename T>
-__global__ __launch_bounds__(ST) SS_NO_PK32 void sample_finish_kernel(
+__global__ __launch_bounds__(ST) FX_NO_PK32 void sample_finish_kernel(
     const T* __restrict__ logits, long ld_row, int V, int G, float inv_temp, int top_k,
     float top_p, const float* __restrict__ uniforms, const float* __restrict__ ws,
     int64_t* __restrict__ out_ids, float* __restrict__ out_lse, float* __restrict__ out_probs) {
@@ -480,7 +474,7 @@ __global__ __launch_bounds__(ST) SS_NO_PK32 void sample_finish_kernel(
   }
 }
 
-__global__ __launch_bounds__(ST) SS_NO_PK32 void coupled_finish_kernel(
+__global__ __launch_bounds__(ST) FX_NO_PK32 void coupled_finish_kernel(
     const float* __restrict__ logits, long ld_row, int V, int G, float inv_temp, int top_k,
     float top_p, const int* __restrict__ steps, const int* __restrict__ rows,
     const int64_t* __restrict__ seed, const float* __restrict__ ws,
@@ -500,7 +494,7 @@ __global__ __launch_bounds__(ST) SS_NO_PK32 void coupled_finish_kernel(
 }
 
 // select_kernel in sampling modes 1 and 2 with the pick from the workspace
-__global__ __launch_bounds__(ST) SS_NO_PK32 void select_finish_kernel(
+__global__ __launch_bounds__(ST) FX_NO_PK32 void select_finish_kernel(
     SelectArgs a, int G, const float* __restrict__ ws) {
   __shared__ Shared s;
   __shared__ FinishShared q;

@@ -448,15 +448,28 @@ def _wscale_ok(fmt, wscale, N, K):
             and (wscale.numel() == N if shape is None else wscale.shape == shape))
 
 
-def _decode_gemv(x, w, wscale, bias, epi, res, qkv_cache, ln, fmt=None):
-    """The body of ``decode_linear`` (``fmt`` None: ``w`` is a 16-bit weight
-    of ``x.dtype``), ``decode_linear_w8`` (``"int8"``: ``w`` int8, ``wscale``
-    fp32 [N]), ``decode_linear_w4`` (``"int4"``: ``w`` packed uint8 [N, K / 2],
-    ``wscale`` fp32 [K / 256, N]) and ``decode_linear_mx4`` (``"mxfp4"``: ``w``
-    packed uint8 [N, K / 2], ``wscale`` uint8 [N, K / 32]): the checks, the QKV
-    unpacking, the output and the call.  None for a call the kernel does not
-    cover; malformed caches / residual assert."""
-    if not x.is_cuda or x.dim() != 2 or x.shape[0] < 1 or x.shape[0] > 16 \
+# kernel family -> (first row, last row -- None: no limit --, takes the ``ln``
+# prologue, takes GV_QKV, binding-name stem, values of a pinned launch shape)
+_FAMILY = {"gemv": (1, 16, True, True, "decode_gemv", 0),
+           "gemm": (17, 64, False, True, "decode_gemm", 2),
+           "prefill": (65, None, False, False, "prefill_gemm", 2)}
+
+
+def _skinny(family, x, w, wscale, bias, epi, res, qkv_cache=None, ln=None, shape=None, fmt=None):
+    """The body of every ``decode_linear*`` (``"gemv"``), ``decode_gemm*``
+    (``"gemm"``) and ``prefill_gemm_w8`` / ``_w4`` / ``_mx4`` (``"prefill"``)
+    call: the checks, the QKV unpacking, the output and the call.  ``fmt``
+    None: ``w`` is a 16-bit weight of ``x.dtype``; ``"int8"``: ``w`` int8,
+    ``wscale`` fp32 [N]; ``"int4"``: ``w`` packed uint8 [N, K / 2], ``wscale``
+    fp32 [K / 256, N]; ``"mxfp4"``: ``w`` packed uint8 [N, K / 2], ``wscale``
+    uint8 [N, K / 32].  None for a call the kernel does not cover; malformed
+    caches / residual assert."""
+    lo, hi, takes_ln, takes_qkv, stem, arity = _FAMILY[family]
+    if fmt is not None and wscale is None:
+        return None
+    if not takes_qkv and epi not in (GV_BIAS, GV_GELU, GV_RES):
+        return None
+    if not x.is_cuda or x.dim() != 2 or x.shape[0] < lo or (hi is not None and x.shape[0] > hi) \
             or x.dtype not in (torch.bfloat16, torch.float16):
         return None
     M, K = x.shape
@@ -477,7 +490,6 @@ def _decode_gemv(x, w, wscale, bias, epi, res, qkv_cache, ln, fmt=None):
                            or ln[0].numel() != K or ln[1].numel() != K
                            or epi not in (GV_GELU, GV_QKV)):
         return None
-    k = _lib.kernels()
     kc = vc = pos = rows = None
     heads = hd = maxlen = 0
     if epi == GV_QKV:
@@ -499,17 +511,22 @@ def _decode_gemv(x, w, wscale, bias, epi, res, qkv_cache, ln, fmt=None):
     if epi == GV_RES:
         assert res is not None and res.shape == (M, N) and res.stride(1) == 1 \
             and res.dtype == x.dtype
-    head = (_lib.dt_code(x.dtype), int(epi), M, N, K, x.data_ptr(), x.stride(0),
-            w.data_ptr(), w.stride(0))
-    tail = (_lib.ptr(bias), _lib.ptr(res) if epi == GV_RES else 0,
-            res.stride(0) if epi == GV_RES else 0, y.data_ptr(), y.stride(0),
-            _lib.ptr(kc), _lib.ptr(vc), _lib.ptr(pos), _lib.ptr(rows), heads, hd, maxlen,
-            _lib.ptr(ln[0]) if ln is not None else 0, _lib.ptr(ln[1]) if ln is not None else 0,
-            float(ln[2]) if ln is not None else 0.0, _lib.stream())
-    if fmt is None:
-        nb = k.decode_gemv(*head, *tail)
-    else:
-        nb = getattr(k, "decode_gemv" + _WFMT[fmt][4])(*head, wscale.data_ptr(), *tail)
+    pin = [int(v) for v in shape] if shape is not None else [0] * arity
+    if len(pin) != arity:
+        raise ValueError("shape: {} values expected, got {}".format(arity, len(pin)))
+    args = [_lib.dt_code(x.dtype), int(epi), M, N, K, x.data_ptr(), x.stride(0),
+            w.data_ptr(), w.stride(0)]
+    if fmt is not None:
+        args.append(wscale.data_ptr())
+    args += [_lib.ptr(bias), _lib.ptr(res) if epi == GV_RES else 0,
+             res.stride(0) if epi == GV_RES else 0, y.data_ptr(), y.stride(0)]
+    if takes_qkv:
+        args += [_lib.ptr(kc), _lib.ptr(vc), _lib.ptr(pos), _lib.ptr(rows), heads, hd, maxlen]
+    if takes_ln:
+        args += [_lib.ptr(ln[0]) if ln is not None else 0, _lib.ptr(ln[1]) if ln is not None else 0,
+                 float(ln[2]) if ln is not None else 0.0]
+    name = stem + (_WFMT[fmt][4] if fmt is not None else "")
+    nb = getattr(_lib.kernels(), name)(*args, *pin, _lib.stream())
     if nb == 0:
         return None
     _lib.maybe_sync()
@@ -533,7 +550,7 @@ def decode_linear(x, weight, bias=None, epi=GV_BIAS, res=None, qkv_cache=None, l
 
     Returns the output, or None when the kernel does not cover the call (the
     caller then uses the general GEMM)."""
-    return _decode_gemv(x, weight, None, bias, epi, res, qkv_cache, ln)
+    return _skinny("gemv", x, weight, None, bias, epi, res, qkv_cache, ln)
 
 
 def decode_linear_w8(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, qkv_cache=None, ln=None):
@@ -545,9 +562,7 @@ def decode_linear_w8(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, qkv_cache=
 
     Returns the output, or None when the kernel does not cover the call (the
     caller then uses the 16-bit weight)."""
-    if wscale is None:
-        return None
-    return _decode_gemv(x, wq, wscale, bias, epi, res, qkv_cache, ln, fmt="int8")
+    return _skinny("gemv", x, wq, wscale, bias, epi, res, qkv_cache, ln, fmt="int8")
 
 
 def decode_linear_w4(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, qkv_cache=None, ln=None):
@@ -560,9 +575,7 @@ def decode_linear_w4(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, qkv_cache=
 
     Returns the output, or None when the kernel does not cover the call (the
     caller then uses the 16-bit weight)."""
-    if wscale is None:
-        return None
-    return _decode_gemv(x, wq, wscale, bias, epi, res, qkv_cache, ln, fmt="int4")
+    return _skinny("gemv", x, wq, wscale, bias, epi, res, qkv_cache, ln, fmt="int4")
 
 
 def decode_linear_mx4(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, qkv_cache=None, ln=None):
@@ -576,75 +589,13 @@ def decode_linear_mx4(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, qkv_cache
 
     Returns the output, or None when the kernel does not cover the call (the
     caller then uses the 16-bit weight)."""
-    if wscale is None:
-        return None
-    return _decode_gemv(x, wq, wscale, bias, epi, res, qkv_cache, ln, fmt="mxfp4")
+    return _skinny("gemv", x, wq, wscale, bias, epi, res, qkv_cache, ln, fmt="mxfp4")
 
 
 # ----------------------------------------------------------------------------
 # the same for 17..64 rows (csrc/kernels/decode_gemm.hip: a register-tiled
 # skinny GEMM over the same weight stream, same weight formats and epilogues)
 # ----------------------------------------------------------------------------
-def _decode_gemm(x, w, wscale, bias, epi, res, qkv_cache, shape, fmt=None):
-    """The body of ``decode_gemm`` / ``decode_gemm_w8`` / ``decode_gemm_w4`` /
-    ``decode_gemm_mx4``, after ``_decode_gemv``: the checks, the QKV unpacking, the output and the
-    call.  None for a call the kernel does not cover; malformed caches /
-    residual assert."""
-    if not x.is_cuda or x.dim() != 2 or x.shape[0] < 17 or x.shape[0] > 64 \
-            or x.dtype not in (torch.bfloat16, torch.float16):
-        return None
-    M, K = x.shape
-    wdtype, wpack = (x.dtype, 1) if fmt is None else _WFMT[fmt][:2]
-    if w.dim() != 2 or w.dtype != wdtype or not w.is_cuda or w.shape[1] * wpack != K:
-        return None
-    N = w.shape[0]
-    if w.stride(1) != 1 or x.stride(1) != 1 or K % 1024 or x.stride(0) % 8 \
-            or (w.stride(0) * w.element_size()) % 16 or w.data_ptr() % 16 or x.data_ptr() % 16:
-        return None
-    if fmt is not None and not _wscale_ok(fmt, wscale, N, K):
-        return None
-    if bias is not None and (bias.dtype != x.dtype or bias.numel() != N
-                             or not bias.is_contiguous()):
-        return None
-    k = _lib.kernels()
-    kc = vc = pos = rows = None
-    heads = hd = maxlen = 0
-    if epi == GV_QKV:
-        kc, vc, pos = qkv_cache[:3]
-        rows = qkv_cache[3] if len(qkv_cache) > 3 else None
-        maxlen, heads, hd = kc.shape[1], kc.shape[2], kc.shape[3]
-        assert N == 3 * heads * hd and kc.is_contiguous() and vc.is_contiguous()
-        assert kc.shape == vc.shape and kc.dtype == x.dtype == vc.dtype
-        assert pos.dtype == torch.int64 and pos.numel() == M and pos.is_contiguous()
-        if rows is None:
-            assert kc.shape[0] >= M
-        else:
-            # rows.max() < kc.shape[0] is the caller's to keep (no sync to check it)
-            assert rows.dtype == torch.int32 and rows.numel() == M and rows.is_contiguous() \
-                and rows.is_cuda
-        y = torch.empty(M, heads * hd, device=x.device, dtype=x.dtype)
-    else:
-        y = torch.empty(M, N, device=x.device, dtype=x.dtype)
-    if epi == GV_RES:
-        assert res is not None and res.shape == (M, N) and res.stride(1) == 1 \
-            and res.dtype == x.dtype
-    nt, ks = shape if shape is not None else (0, 0)
-    head = (_lib.dt_code(x.dtype), int(epi), M, N, K, x.data_ptr(), x.stride(0),
-            w.data_ptr(), w.stride(0))
-    tail = (_lib.ptr(bias), _lib.ptr(res) if epi == GV_RES else 0,
-            res.stride(0) if epi == GV_RES else 0, y.data_ptr(), y.stride(0),
-            _lib.ptr(kc), _lib.ptr(vc), _lib.ptr(pos), _lib.ptr(rows), heads, hd, maxlen,
-            int(nt), int(ks), _lib.stream())
-    if fmt is None:
-        nb = k.decode_gemm(*head, *tail)
-    else:
-        nb = getattr(k, "decode_gemm" + _WFMT[fmt][4])(*head, wscale.data_ptr(), *tail)
-    if nb == 0:
-        return None
-    _lib.maybe_sync()
-    return y
-
-
 def decode_gemm(x, weight, bias=None, epi=GV_BIAS, res=None, qkv_cache=None, shape=None):
     """``decode_linear`` for 17 <= M <= 64 rows: ``x [M, K] @ weight[N, K]^T``
     on the register-tiled skinny GEMM, which streams the weight once for all
@@ -658,30 +609,24 @@ def decode_gemm(x, weight, bias=None, epi=GV_BIAS, res=None, qkv_cache=None, sha
 
     Returns the output, or None when the kernel does not cover the call (the
     caller then uses the general GEMM)."""
-    return _decode_gemm(x, weight, None, bias, epi, res, qkv_cache, shape)
+    return _skinny("gemm", x, weight, None, bias, epi, res, qkv_cache, shape=shape)
 
 
 def decode_gemm_w8(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, qkv_cache=None, shape=None):
     """``decode_gemm`` with the weight-only int8 weight of ``decode_linear_w8``."""
-    if wscale is None:
-        return None
-    return _decode_gemm(x, wq, wscale, bias, epi, res, qkv_cache, shape, fmt="int8")
+    return _skinny("gemm", x, wq, wscale, bias, epi, res, qkv_cache, shape=shape, fmt="int8")
 
 
 def decode_gemm_w4(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, qkv_cache=None, shape=None):
     """``decode_gemm`` with the weight-only int4 weight (group size 256) of
     ``decode_linear_w4``."""
-    if wscale is None:
-        return None
-    return _decode_gemm(x, wq, wscale, bias, epi, res, qkv_cache, shape, fmt="int4")
+    return _skinny("gemm", x, wq, wscale, bias, epi, res, qkv_cache, shape=shape, fmt="int4")
 
 
 def decode_gemm_mx4(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, qkv_cache=None, shape=None):
     """``decode_gemm`` with the weight-only MXFP4 weight of ``decode_linear_mx4``;
     every tile shape up to ``nt = 4`` at 64 rows."""
-    if wscale is None:
-        return None
-    return _decode_gemm(x, wq, wscale, bias, epi, res, qkv_cache, shape, fmt="mxfp4")
+    return _skinny("gemm", x, wq, wscale, bias, epi, res, qkv_cache, shape=shape, fmt="mxfp4")
 
 
 # ----------------------------------------------------------------------------
@@ -689,45 +634,6 @@ def decode_gemm_mx4(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, qkv_cache=N
 # tiled GEMM with the weight operand stationary in registers and the
 # activations staged through LDS; GV_BIAS / GV_GELU / GV_RES, no QKV scatter)
 # ----------------------------------------------------------------------------
-def _prefill_gemm(x, w, wscale, bias, epi, res, shape, fmt):
-    """The body of ``prefill_gemm_w8`` / ``prefill_gemm_w4`` /
-    ``prefill_gemm_mx4``, after ``_decode_gemm``: the checks, the output and
-    the call.  None for a call the kernel does not cover; a malformed residual
-    asserts."""
-    if wscale is None or epi not in (GV_BIAS, GV_GELU, GV_RES):
-        return None
-    if not x.is_cuda or x.dim() != 2 or x.shape[0] < 65 \
-            or x.dtype not in (torch.bfloat16, torch.float16):
-        return None
-    M, K = x.shape
-    wdtype, wpack = _WFMT[fmt][:2]
-    if w.dim() != 2 or w.dtype != wdtype or not w.is_cuda or w.shape[1] * wpack != K:
-        return None
-    N = w.shape[0]
-    if w.stride(1) != 1 or x.stride(1) != 1 or K % 1024 or x.stride(0) % 8 \
-            or (w.stride(0) * w.element_size()) % 16 or w.data_ptr() % 16 or x.data_ptr() % 16:
-        return None
-    if not _wscale_ok(fmt, wscale, N, K):
-        return None
-    if bias is not None and (bias.dtype != x.dtype or bias.numel() != N
-                             or not bias.is_contiguous()):
-        return None
-    y = torch.empty(M, N, device=x.device, dtype=x.dtype)
-    if epi == GV_RES:
-        assert res is not None and res.shape == (M, N) and res.stride(1) == 1 \
-            and res.dtype == x.dtype
-    mt, nt = shape if shape is not None else (0, 0)
-    nb = getattr(_lib.kernels(), "prefill_gemm" + _WFMT[fmt][4])(
-        _lib.dt_code(x.dtype), int(epi), M, N, K, x.data_ptr(), x.stride(0), w.data_ptr(),
-        w.stride(0), wscale.data_ptr(), _lib.ptr(bias), _lib.ptr(res) if epi == GV_RES else 0,
-        res.stride(0) if epi == GV_RES else 0, y.data_ptr(), y.stride(0), int(mt), int(nt),
-        _lib.stream())
-    if nb == 0:
-        return None
-    _lib.maybe_sync()
-    return y
-
-
 def prefill_gemm_w8(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, shape=None):
     """``x [M, K] @ (wq[N, K] * wscale[N, None])^T`` for M >= 65 rows on the
     int8 copy ``decode_linear_w8`` streams, with the epilogue ``epi``: GV_BIAS
@@ -743,18 +649,18 @@ def prefill_gemm_w8(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, shape=None)
 
     Returns the output, or None when the kernel does not cover the call (the
     caller then uses the 16-bit weight)."""
-    return _prefill_gemm(x, wq, wscale, bias, epi, res, shape, "int8")
+    return _skinny("prefill", x, wq, wscale, bias, epi, res, shape=shape, fmt="int8")
 
 
 def prefill_gemm_w4(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, shape=None):
     """``prefill_gemm_w8`` on the int4 copy (group size 256) of
     ``decode_linear_w4``; it has no (8, 4) tile."""
-    return _prefill_gemm(x, wq, wscale, bias, epi, res, shape, "int4")
+    return _skinny("prefill", x, wq, wscale, bias, epi, res, shape=shape, fmt="int4")
 
 
 def prefill_gemm_mx4(x, wq, wscale, bias=None, epi=GV_BIAS, res=None, shape=None):
     """``prefill_gemm_w8`` on the MXFP4 copy of ``decode_linear_mx4``."""
-    return _prefill_gemm(x, wq, wscale, bias, epi, res, shape, "mxfp4")
+    return _skinny("prefill", x, wq, wscale, bias, epi, res, shape=shape, fmt="mxfp4")
 
 
 # ----------------------------------------------------------------------------

@@ -7,7 +7,7 @@ import functools
 import pytest
 import torch
 
-from tests.gemv_cases import _int_case
+from tests.gemv_cases import _check_front_end_rejects, _int_case
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -173,3 +173,4 @@ def test_decode_gemm_uncovered_calls_return_none():
     assert G.decode_gemm_w8(x, w, torch.ones(64, device=DEV)) is None  # not int8
     with pytest.raises(AssertionError):                                # never reaches the binding
         G.decode_gemm(x, w, None, G.GV_RES)
+    _check_front_end_rejects(17, G.decode_gemm_w8, G.decode_gemm)

@@ -4,7 +4,7 @@ decode layer against the unfused op chain."""
 import pytest
 import torch
 
-from tests.gemv_cases import _int_case
+from tests.gemv_cases import _check_front_end_rejects, _int_case
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -88,6 +88,7 @@ def test_decode_gemv_uncovered_calls_return_none():
     assert G.decode_linear(x, w.half()) is None                        # weight dtype != x dtype
     with pytest.raises(AssertionError):                                # never reaches the binding
         G.decode_linear(x, w, None, G.GV_RES)
+    _check_front_end_rejects(16, G.decode_linear_w8, G.decode_linear)
 
 
 def test_decode_gemv_fused_layernorm_lds_opt_in_boundary():

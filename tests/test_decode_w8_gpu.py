@@ -7,7 +7,7 @@ import copy
 import pytest
 import torch
 
-from tests.gemv_cases import _int_case
+from tests.gemv_cases import _check_front_end_rejects, _int_case
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -109,6 +109,7 @@ def test_w8_uncovered_calls_return_none():
     assert G.decode_linear_w8(torch.zeros(2, 1024, device=DEV), q, s) is None      # fp32 x
     assert G.decode_linear_w8(torch.zeros(2, 1024, device=DEV, dtype=torch.bfloat16),
                               q.bfloat16(), s) is None                 # not an int8 weight
+    _check_front_end_rejects(16, G.decode_linear_w8)
 
 
 # ----------------------------------------------------------------------------

@@ -7,7 +7,7 @@ import functools
 import pytest
 import torch
 
-from tests.gemv_cases import _int_case
+from tests.gemv_cases import _check_front_end_rejects, _int_case
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -154,3 +154,4 @@ def test_prefill_gemm_uncovered_calls_return_none():
     assert G.prefill_gemm_w4(torch.zeros(65, 1024, **bf), p, torch.ones(64, 4, device=DEV)) is None
     assert G.prefill_gemm_mx4(torch.zeros(65, 1024, **bf), p,
                               torch.full((64, 16), 127, device=DEV, dtype=torch.uint8)) is None
+    _check_front_end_rejects(65, G.prefill_gemm_w8)
